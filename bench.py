@@ -6,7 +6,7 @@
                                                           bench.py itself -- the same launcher on 127.0.0.1)
 
 metric  : residual+Jacobian evaluations per second (BASELINE.json `metric`, first component); LM iterations/s and
-          the final reprojection RMS of a full solve are reported alongside in the same JSON line.
+          the final reprojection RMS of a full solve are reported alongside in the same JSON line with --full.
 step    : ONE fused residual+Jacobian evaluation reduced to the normal equations at one x -- table preparation,
           k_linearize (MFMA), assembly into H_ss / H_fs / H_ff / g, and (N > 1) the all-reduce of [g | diag | cost]:
           what one scipy `jac` call (1 + 34 finite-difference `evaluate` calls) plus J^T J / J^T f costs the reference.
@@ -28,6 +28,13 @@ parity  : `parity_route` = the solver that REPRODUCES THE REFERENCE'S END POINT 
           very rig (tests/golden/cfg3_endpoint.npz: Calibration.bundle_adjust() run to completion on one host core,
           oracle/make_endpoint.py), beside the reference's measured wall time.  `lm_iters_per_s` / `lm_long_solve` belong to the
           exact-step solver (solver = "native"), which ends at the converged optimum instead.
+plain   : a plain run sets up, warms up, times exactly K steps (one timed region), writes --dump-outputs if given and prints the
+          line: `metric`, `value`, `unit`, `ms_per_step`, `config` and what derives from the timed region alone (`obs_per_s`,
+          `step_roofline_frac`, `timed_regions_ms`).  --full adds everything else above -- `--repeats`
+          regions (default 5, median reported), `weak_scaling`, `host_boundary`, `roofline`, the solves, `parity_route`,
+          `scipy_mode`, `cpu_baseline` -- each as documented.
+outputs : --dump-outputs DIR writes what the last timed step computed, as float64 .npy files (see dump_outputs); the rig is seeded,
+          so the same arguments give the same inputs on every run and two builds can be compared output for output.
 """
 import argparse
 import json
@@ -164,6 +171,42 @@ def cpu_baseline(n_frames_sample=25, full_jacobian=False):
                        f"(J v + J^T u) = {t_lsmr_iter * 1e3:.1f} ms on the sample; the measured full-size figure is `reference_measured`"))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, h, calib, x0, n_frames, write=True):
+  """--dump-outputs DIR: the normal equations of the last timed step, as a caller of the evaluation receives them (float64).
+
+  H = J^T J is read back from HBM as the last timed step left it (mcba_dense_hessian) and stored by its blocks, every entry the
+  block form holds: H_ss (shared x shared), H_fs (frame x shared parameters) and H_ff (the per-frame diagonal blocks, [F, p, p]).
+  g = J^T f, diag(J^T J) and the cost come through the host boundary at the same x (mcba_normal_equations: the same kernels,
+  equal bit for bit to the device-resident step, tests/test_gpu_parity.py::test_device_resident_evaluation_equals_host_boundary_evaluation).
+  N > 1: every rank takes part (the host boundary reduces over ranks); rank 0 writes, its H blocks are those of its shard."""
+  from multical_amd.backend import PARAM_ORDER
+  h.synchronize()
+  H = h.dense_hessian()
+  cost, g, diag = h.normal_equations(x0)
+  if not write:
+    return None
+  n = H.shape[0]
+  on = [k for k in PARAM_ORDER if calib.optimize[k] is True]
+  sizes = dict(zip(PARAM_ORDER, h.problem.block_sizes))
+  f0 = sum(sizes[k] for k in on[:on.index("motion")]) if "motion" in on else 0
+  nf = sizes["motion"] if "motion" in on else 0
+  assert nf % (6 * n_frames) == 0 and sum(sizes[k] for k in on) == n, (nf, n_frames, n)
+  # the motion block is [part][frame][6] (rolling shutter: every pose, then every velocity): frame k's parameters, in order
+  frame_idx = f0 + np.arange(nf).reshape(-1, n_frames, 6).transpose(1, 0, 2).reshape(n_frames, -1)
+  shared = np.r_[0:f0, f0 + nf:n]
+  out = dict(cost=np.array([cost]), g=g, diag=diag, H_ss=H[np.ix_(shared, shared)], H_fs=H[frame_idx.ravel()][:, shared],
+             H_ff=H[frame_idx[:, :, None], frame_idx[:, None, :]])
+  total = sum(a.size * 8 for a in out.values())
+  assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+  os.makedirs(out_dir, exist_ok=True)
+  for name, a in out.items():
+    np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+  return sorted(out)
+
+
 def self_launch(args):
   """`python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU) through
   torch.distributed.run on the loopback address, exactly as the driver's multi-GPU command line does, and pass rank 0's
@@ -288,7 +331,13 @@ def main():
   ap.add_argument("--gpus", type=int, default=1)
   ap.add_argument("--steps", type=int, default=200)
   ap.add_argument("--warmup", type=int, default=20)
-  ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the median is reported")
+  ap.add_argument("--repeats", type=int, default=None,
+                  help="timed regions of --steps steps each; the median is reported (default: 1; with --full: 5)")
+  ap.add_argument("--full", action="store_true",
+                  help="everything beyond the headline: weak scaling, host boundary, roofline, solves, parity route, scipy mode, "
+                       "cpu baseline (the --no-* options below select among them)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write the normal equations of the last timed step to DIR/<name>.npy (float64)")
   ap.add_argument("--config", choices=sorted(RIGS), default="cfg3", help="cfg3 = BASELINE configs[2] (north star), cfg4 = configs[3]")
   ap.add_argument("--no-cpu-baseline", action="store_true")
   ap.add_argument("--cpu-baseline-full", action="store_true",
@@ -307,6 +356,10 @@ def main():
                        "its real message, barrier + MAX timing, watchdog, JSON line) with the shard evaluated by tests/hostmath on the CPU")
   ap.add_argument("--dry-frames", type=int, default=14, help="--dry-run: frames of the (cut-down) rig")
   args = ap.parse_args()
+  if args.repeats is None:
+    args.repeats = 5 if args.full else 1
+  if args.dry_run and args.dump_outputs:
+    ap.error("--dump-outputs writes what the device computed; --dry-run has no device")
   if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
     sys.exit(self_launch(args))
   if args.dry_run:
@@ -500,8 +553,12 @@ def main():
     watchdog.daemon = True
     watchdog.start()
 
+  # ---- what the last timed step computed (before any other evaluation touches the handle) ----------------------------
+  if args.dump_outputs:
+    dump_outputs(args.dump_outputs, h, calib, x0, F_rig, write=rank == 0)
+
   # ---- weak scaling (N > 1): every rank owns a full F_rig-frame shard of one N-times-longer rig --------------------
-  if world > 1 and not args.no_weak:
+  if args.full and world > 1 and not args.no_weak:
     wshard = (rank * F_rig, (rank + 1) * F_rig)
     wrig, wcalib, hw, wnative = make_handle(F_rig * world, wshard)
     wx = np.ascontiguousarray(wcalib.param_vec)
@@ -513,35 +570,37 @@ def main():
                      "with the all-reduce of the shared [g | diag | cost]")
     hw.close()
   # PCIe-inclusive variant (never `value`): every evaluation enters and leaves through the host boundary
-  host_ms_per_step = timed(step_host) / args.steps * 1e3
+  if args.full:
+    host_ms_per_step = timed(step_host) / args.steps * 1e3
 
-  # ---- dominant kernel: k_linearize, HIP events on the handle's stream (this rank's shard) --------------------------
-  lin_ms = h.time_linearize(x0, repeats=50)
-  res_ms = h.time_residuals(x0, repeats=50)
-  alg_bytes = 17 * n_slots_local + 16 * n_obs_local      # observed xy + mask per slot, residual per obs
-  achieved = alg_bytes / (lin_ms * 1e-3) / 1e9
   d = h.problem
   NV = (12 if d.motion == 1 else 6) + (4 + d.n_dist if d.optimize & 8 else 0) + 1
   flops_per_obs = 2 * NV * (NV + 1) + 420 + (260 if d.motion == 1 else 0)
   n_flops_obs[0] = flops_per_obs
-  alg_flops = n_obs_local * flops_per_obs
-  # The fused pass is FP64-bound (~23 flop per algorithmic byte against a ridge of ~10 flop/B), so the
-  # roofline that bounds k_linearize is the FP64 matrix/vector peak; the HBM view of the same launch is kept alongside.
-  tflops = alg_flops / (lin_ms * 1e-3) / 1e12
-  roofline = dict(bound="mfma", kernel="k_linearize", achieved=tflops, peak=FP64_PEAK_TFLOPS, unit="TFLOP/s",
-                  frac=tflops / FP64_PEAK_TFLOPS, traffic=None, launch_ms=lin_ms, algorithmic_flops=alg_flops,
-                  algorithmic_bytes=alg_bytes,
-                  hbm=dict(achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS),
-                  residual_kernel=dict(bound="hbm", launch_ms=res_ms, counter_bytes=None, achieved=None, frac=None,
-                                       note="k_residual gathers the observations of the inlier slots only (mask bytes compacted "
-                                            "per view), so its traffic is taken from the PMC counters of the committed profile "
-                                            "(profiles/hbm_traffic.json: FETCH_SIZE x2 + WRITE_SIZE), not from the algorithmic "
-                                            "17 B / slot + 16 B / observation, which it does not move"))
+  # ---- dominant kernel: k_linearize, HIP events on the handle's stream (this rank's shard) --------------------------
+  if args.full:
+    lin_ms = h.time_linearize(x0, repeats=50)
+    res_ms = h.time_residuals(x0, repeats=50)
+    alg_bytes = 17 * n_slots_local + 16 * n_obs_local      # observed xy + mask per slot, residual per obs
+    achieved = alg_bytes / (lin_ms * 1e-3) / 1e9
+    alg_flops = n_obs_local * flops_per_obs
+    # The fused pass is FP64-bound (~23 flop per algorithmic byte against a ridge of ~10 flop/B), so the
+    # roofline that bounds k_linearize is the FP64 matrix/vector peak; the HBM view of the same launch is kept alongside.
+    tflops = alg_flops / (lin_ms * 1e-3) / 1e12
+    roofline = dict(bound="mfma", kernel="k_linearize", achieved=tflops, peak=FP64_PEAK_TFLOPS, unit="TFLOP/s",
+                    frac=tflops / FP64_PEAK_TFLOPS, traffic=None, launch_ms=lin_ms, algorithmic_flops=alg_flops,
+                    algorithmic_bytes=alg_bytes,
+                    hbm=dict(achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS),
+                    residual_kernel=dict(bound="hbm", launch_ms=res_ms, counter_bytes=None, achieved=None, frac=None,
+                                         note="k_residual gathers the observations of the inlier slots only (mask bytes compacted "
+                                              "per view), so its traffic is taken from the PMC counters of the committed profile "
+                                              "(profiles/hbm_traffic.json: FETCH_SIZE x2 + WRITE_SIZE), not from the algorithmic "
+                                              "17 B / slot + 16 B / observation, which it does not move"))
   # HBM bytes per launch from the PMC counters: they cannot be read inside an un-profiled run, so the figure of the
   # committed rocprofv3 passes of the same command is quoted and labelled as such (profiles/hbm_traffic.json: separate
   # --pmc FETCH_SIZE / WRITE_SIZE passes, gfx950 x2 read correction)
   traffic_file = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-  if os.path.exists(traffic_file) and world == 1 and args.config == "cfg3":
+  if roofline is not None and os.path.exists(traffic_file) and world == 1 and args.config == "cfg3":
     try:
       tj = json.load(open(traffic_file))
       roofline["traffic"] = tj.get("k_linearize_bytes_per_launch")
@@ -564,7 +623,7 @@ def main():
 
   # ---- LM iterations/s and final RMS: one full bundle adjustment of the same problem (not part of `value`) --------
   ref_end = reference_endpoint(args.config)
-  if not args.no_solve:
+  if args.full and not args.no_solve:
     # the default-tolerance solve of the rig with the EXACT-step solver (scipy's defaults: ftol 1e-4), repeated: median of the
     # repeats; and a LONG solve (tight tolerances, fixed number of trial steps from a perturbed start) whose per-trial-step time is
     # the steady-state figure
@@ -601,7 +660,7 @@ def main():
                                                  bytes_per_trial_step=8 * doubles / max(lres.nfev - 1, 1),
                                                  message_doubles=sorted(set(abs(s) for s in sizes)))
   # collectives of ONE evaluation step (N > 1)
-  if world > 1:
+  if args.full and world > 1:
     h.allreduce_stats(reset=True)
     step()
     barrier()
@@ -609,7 +668,7 @@ def main():
     step_comm = dict(allreduce_calls=calls, allreduce_bytes=8 * doubles, message_doubles=[abs(s) for s in sizes])
 
   # ---- PARITY ROUTE: the solver that reproduces the reference's END POINT, on the whole rig (single GPU or frame-sharded) -----
-  if not args.no_lsmr_mode and not args.no_solve:
+  if args.full and not args.no_lsmr_mode and not args.no_solve:
     h.solve(x0, tr_solver="lsmr")                                   # warm-up (buffers, first-use allocations)
     runs = []
     for _ in range(3):
@@ -692,7 +751,7 @@ def main():
                                           fp64_frac=fl / (parity_route["us_per_lsmr_iteration"] * 1e-6) / 1e12 / FP64_PEAK_TFLOPS)
 
   # ---- the reference's own solver on the device functions (product mode solver="scipy"), beside the native solve -----
-  if world == 1 and not args.no_scipy_mode and args.config == "cfg3":
+  if args.full and world == 1 and not args.no_scipy_mode and args.config == "cfg3":
     srig = synthetic.make_rig("cfg3", frames=args.scipy_frames)
     sc = calibration.from_rig(srig)
     with Handle(lower(sc)) as hsm:
@@ -720,7 +779,7 @@ def main():
   out = None
   if rank == 0:
     out = assemble()
-    if world == 1 and not args.no_cpu_baseline and args.config == "cfg3":
+    if args.full and world == 1 and not args.no_cpu_baseline and args.config == "cfg3":
       out["cpu_baseline"] = cpu_baseline(full_jacobian=args.cpu_baseline_full)
       if ref_end is not None:
         # the REAL reference, run to completion on this rig (build container): njev Jacobians (= residual+Jacobian evaluations by

@@ -5,7 +5,7 @@
 set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r4p; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --no-scipy-mode --no-lsmr-mode"
+B="python $R/bench.py --full --no-scipy-mode --no-lsmr-mode"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o trace -- $B --steps 200 --warmup 20 > $O/bench_traced.json 2> $O/bench_traced.err
 # PMC: counters in their own passes, kernel trace only (no other trace domain)
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc -o pmc_fetch -- $B --steps 30 --warmup 5 --repeats 1 --no-cpu-baseline --no-solve > /dev/null 2> $O/pmc1.err
@@ -18,7 +18,7 @@ for C in FETCH_SIZE WRITE_SIZE; do
   PYTHONPATH=$R:$R/tests rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/spmc_$C -o pmc -- python $R/profiles/scripts/prof_cfg.py cfg3 > $O/spmc_$C.log 2>&1
 done
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -c 300 $O/bench.json
 python profiles/scripts/prof_linearize.py > $O/lin_phases.log 2>&1; tail -12 $O/lin_phases.log
 for CFG in cfg3 cfg4 cfg2; do MCBA_TIMING=1 python profiles/scripts/prof_workspace.py $CFG > $O/workspace_$CFG.log 2>&1; grep "calibrate ms" $O/workspace_$CFG.log; done

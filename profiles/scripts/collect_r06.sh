@@ -6,7 +6,7 @@ set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6p; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$R:$R/tests
-B="python $R/bench.py --no-scipy-mode --no-lsmr-mode"
+B="python $R/bench.py --full --no-scipy-mode --no-lsmr-mode"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o trace -- $B --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_traced.json 2> $O/bench_traced.err
 # PMC: counters in their own passes, kernel trace only (no other trace domain)
 timeout 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc -o pmc_fetch -- $B --steps 30 --warmup 5 --repeats 1 --no-cpu-baseline --no-solve > /dev/null 2> $O/pmc1.err
@@ -26,10 +26,10 @@ done
 cd $R; timeout 120 python profiles/scripts/prof_lsmr_iter.py cfg3 cfg4 cfg5 cfg2 > $O/lsmr_iteration.log 2>&1; cut -c1-400 $O/lsmr_iteration.log
 fi
 cd $R
-timeout 400 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 400 python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -c 300 $O/bench.json
 if [ "$1" != "bench" ]; then
-timeout 200 python bench.py --config cfg4 --no-cpu-baseline --no-scipy-mode > $O/bench_cfg4.json 2> $O/bench_cfg4.err
+timeout 200 python bench.py --full --config cfg4 --no-cpu-baseline --no-scipy-mode > $O/bench_cfg4.json 2> $O/bench_cfg4.err
 for CFG in cfg3 cfg4 cfg2; do
   MCBA_TIMING=1 timeout 100 python profiles/scripts/prof_workspace.py $CFG --solver native > $O/workspace_$CFG.log 2>&1; grep "calibrate ms" $O/workspace_$CFG.log
   timeout 100 python profiles/scripts/prof_workspace.py $CFG --solver lsmr > $O/workspace_lsmr_$CFG.log 2>&1; grep "calibrate ms" $O/workspace_lsmr_$CFG.log

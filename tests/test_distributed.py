@@ -475,7 +475,7 @@ def test_bench_two_ranks_on_one_gpu():
   the frame-sharded rig -- lands on the committed end point of the unmodified reference."""
   import json
   r = _run_bench({"MCBA_BENCH_BACKEND": "gloo"}, "--gpus", "2", "--steps", "5", "--warmup", "2", "--repeats", "2",
-                 "--no-cpu-baseline")
+                 "--no-cpu-baseline", "--full")
   assert r.returncode == 0, r.stderr[-3000:]
   assert "[bench rank 0/2]" in r.stderr and "[bench rank 1/2]" in r.stderr and "native_rccl=false" in r.stderr
   line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
