@@ -224,7 +224,8 @@ int32_t mcba_set_log(mcba_handle h, mcba_log_fn fn, void* ctx);
 /* Calibration.adjust_outliers (calibration.py:254-268; what Workspace.calibrate drives, workspace.py:238-244) in ONE call:
  * `num_adjustments` rounds of {report, optional f_scale = quantile(errors, scale_quantile) * scale_factor, reject_outliers at
  * quantile(errors, outlier_quantile) * outlier_factor, bundle_adjust}, then the final report.  rounds[num_adjustments + 1];
- * a negative factor disables that step; inliers_out (may be NULL) receives the final mask [C,F,B,P].                  */
+ * a negative factor disables that step; inliers_out (may be NULL) receives the final mask [C,F,B,P]
+ * (complete on every rank of a frame-sharded problem: mcba_gather_inliers).                                       */
 int32_t mcba_adjust_outliers(mcba_handle h, double* x_inout, const mcba_options* opt, int32_t num_adjustments,
                              double outlier_quantile, double outlier_factor, double scale_quantile, double scale_factor,
                              mcba_round_report* rounds, uint8_t* inliers_out);
@@ -256,8 +257,14 @@ int32_t mcba_error_count(mcba_handle h, int32_t inliers_only, int64_t* n);
 /* Calibration.reject_outliers on the device (calibration.py:240-252): inliers = (err < threshold) & valid at x;
  * replaces the handle's inlier table.  n_inliers / n_valid (over all ranks) may be NULL.                            */
 int32_t mcba_reject_outliers(mcba_handle h, const double* x, double threshold, int64_t* n_inliers, int64_t* n_valid);
-/* current inlier table in the reference's [C,F,B,P] order                                                         */
+/* current inlier table in the reference's [C,F,B,P] order (a frame-sharded handle writes its own frames only, the
+ * others are zero)                                                                                                 */
 int32_t mcba_get_inliers(mcba_handle h, uint8_t* mask);
+/* the COMPLETE inlier table in [C,F,B,P] order on every rank of a frame-sharded problem: each rank packs the bits of its
+ * own frames 32 per double, ONE sum-all-reduce of ceil(C F B P / 32) doubles through the hook / RCCL ORs them (the
+ * bits are disjoint, every word is an integer below 2^32), unpacked on the device.  Collective: every rank calls it.
+ * On a handle that is not sharded it is mcba_get_inliers.                                                           */
+int32_t mcba_gather_inliers(mcba_handle h, uint8_t* mask);
 
 /* Projected points [C,F,B,P,2] of Calibration.reprojected (calibration.py:124-130).                            */
 int32_t mcba_project(mcba_handle h, const double* x, double* projected);

@@ -90,6 +90,7 @@ SYMBOLS = [
   ("mcba_error_count", C.c_int32, [H, C.c_int32, C.POINTER(C.c_int64)]),
   ("mcba_reject_outliers", C.c_int32, [H, c_double_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
   ("mcba_get_inliers", C.c_int32, [H, c_uint8_p]),
+  ("mcba_gather_inliers", C.c_int32, [H, c_uint8_p]),
   ("mcba_adjust_outliers", C.c_int32, [H, c_double_p, C.POINTER(Options), C.c_int32, C.c_double, C.c_double, C.c_double,
                                        C.c_double, C.POINTER(RoundReport), c_uint8_p]),
   ("mcba_normal_equations", C.c_int32, [H, c_double_p, C.POINTER(Options), c_double_p, c_double_p, c_double_p]),

@@ -396,8 +396,16 @@ class Handle(object):
     return x, out, mask
 
   def get_inliers(self):
+    """the inlier table [C,F,B,P]; a frame-sharded handle fills its own frames only (see gather_inliers)"""
     m = np.empty(self.shape, dtype=np.bool_)      # the device writes 0 / 1 bytes: a bool array without a second copy
     check(self.lib.mcba_get_inliers(self.h, _ptr(m.view(np.uint8), C.c_uint8)))
+    return m
+
+  def gather_inliers(self):
+    """the COMPLETE inlier table [C,F,B,P] on every rank of a frame-sharded problem (mcba_gather_inliers: one collective of
+    ceil(C F B P / 32) doubles -- every rank must call it); get_inliers() on a plain handle"""
+    m = np.empty(self.shape, dtype=np.bool_)
+    check(self.lib.mcba_gather_inliers(self.h, _ptr(m.view(np.uint8), C.c_uint8)))
     return m
 
   def linearize_profile(self, x, with_tmat=False):

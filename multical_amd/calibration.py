@@ -19,7 +19,7 @@ from functools import cached_property
 
 import numpy as np
 
-from . import parameters
+from . import distributed, parameters
 from .backend import Handle, lower
 from .structs import Struct, Table, struct, choose, subset
 
@@ -77,6 +77,15 @@ def get_solver():
   return _default_solver[0]
 
 
+_scipy_unsharded_noted = [False]
+
+
+def _note_scipy_unsharded():
+  if distributed.sharding_enabled() and not _scipy_unsharded_noted[0]:
+    _scipy_unsharded_noted[0] = True
+    logger.info("multical_amd: solver 'scipy' is not frame-sharded: every rank solves the whole rig")
+
+
 def fused_outlier_loop_off():
   """MULTICAL_AMD_FUSED_LOOP=0: adjust_outliers as a Python loop over report / reject_outliers / bundle_adjust on new Calibration
   objects (the reference's structure, step by step) instead of one mcba_adjust_outliers call."""
@@ -118,12 +127,17 @@ class _HandleCache(object):
     # a token compared with `is` first: hashing 2.6 MB of mask bytes on every lookup cost 0.6 ms x 16 lookups per
     # Workspace.calibrate.
     self.entries = []
+    # frame-sharded handles (multical_amd.distributed.sharding) live in a list of their own, keyed additionally by group, world size
+    # and shard plan.  Their inputs are replicated, so hits, misses and evictions are the same on every rank -- creation is collective.
+    self.sharded = []
 
   @staticmethod
   def _same_array(a, b):
     return a is b or (a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b))
 
-  def get(self, calib):
+  def get(self, calib, sharded=False):
+    """(handle, lowered problem) of `calib`; sharded=True: a frame-sharded handle while multical_amd.distributed.sharding is on with
+    more than one rank (otherwise the plain one)."""
     prob = getattr(calib, "_mcba_problem", None)     # Calibration objects are immutable: lower once per object
     if prob is None:
       prob = lower(calib)
@@ -136,8 +150,15 @@ class _HandleCache(object):
            None if prob.camera_fisheye is None else prob.camera_fisheye.tobytes(), prob.fix_aspect.tobytes(),
            prob.camera_valid.tobytes(), prob.frame_valid.tobytes(), prob.board_valid.tobytes(),
            prob.board_sizes.tobytes(), prob.image_heights.tobytes())
+    cfg = distributed.shard_config() if sharded else None
+    entries = self.entries
+    if cfg is not None:
+      group, world, native, balance = cfg
+      plan = distributed.shard_plan(calib, world, balance)
+      key = key + ("sharded", id(group), world, tuple(plan))
+      entries = self.sharded
     points, valid = calib.point_table.points, calib.point_table.valid
-    for i, e in enumerate(self.entries):
+    for i, e in enumerate(entries):
       h = e["handle"]
       if e["key"] == key and h.h and self._same_array(e["points"], points) and self._same_array(e["valid"], valid) \
           and np.array_equal(self._constants(calib, prob, e["x_full"]), self._constants(calib, prob, prob.x_full)) \
@@ -148,10 +169,15 @@ class _HandleCache(object):
             h.set_inliers(mask)
           e["mask"] = mask
         return h, prob
-    h = Handle(prob)
-    self.entries.append(dict(key=key, points=points, valid=valid, x_full=prob.x_full, handle=h, mask=calib.inlier_mask))
-    while len(self.entries) > self.capacity:
-      self.entries.pop(0)["handle"].close()
+    if cfg is None:
+      h = Handle(prob)
+    else:
+      distributed.agree_on_plan(plan, group)        # once per handle, before the collective creation
+      h = distributed.sharded_handle(calib, group=group, native=native, shards=plan, problem=prob)
+      h.shard_group = group
+    entries.append(dict(key=key, points=points, valid=valid, x_full=prob.x_full, handle=h, mask=calib.inlier_mask))
+    while len(entries) > self.capacity:
+      entries.pop(0)["handle"].close()
     return h, prob
 
   @staticmethod
@@ -166,7 +192,7 @@ class _HandleCache(object):
 
   def note_inliers(self, handle, mask):
     """the device already holds `mask` (set by reject_outliers): remember its token so it is not uploaded again."""
-    for e in self.entries:
+    for e in self.entries + self.sharded:
       if e["handle"] is handle:
         e["mask"] = mask
 
@@ -175,10 +201,21 @@ class _HandleCache(object):
     device mask is unknown, so the next lookup must upload its own (a fresh token never compares equal)."""
     self.note_inliers(handle, _UNKNOWN_MASK)
 
+  def close_sharded(self, group=None):
+    """close the sharded handles of `group` (leaving multical_amd.distributed.sharding)"""
+    keep = []
+    for e in self.sharded:
+      if getattr(e["handle"], "shard_group", None) is group:
+        e["handle"].close()
+      else:
+        keep.append(e)
+    self.sharded = keep
+
   def clear(self):
-    for e in self.entries:
+    for e in self.entries + self.sharded:
       e["handle"].close()
     self.entries = []
+    self.sharded = []
 
 
 def parameters_order():
@@ -265,12 +302,14 @@ class Calibration(parameters.Parameters):
                      motion=self.motion.pre_transform(t))
 
   # --- device evaluation ------------------------------------------------------------------------------------
-  def _handle(self):
-    return handle_cache.get(self)[0]
+  def _handle(self, sharded=False):
+    """the cached device handle; sharded=True: frame-sharded while multical_amd.distributed.sharding is on (solves, outlier loop and
+    statistics).  The accessors that return per-point arrays always use the plain handle."""
+    return handle_cache.get(self, sharded)[0]
 
   @cached_property
   def reprojected(self):
-    """calibration.py:124-130 (rolling-shutter scan time from the measured points)."""
+    """calibration.py:124-130 (rolling-shutter scan time from the measured points).  Per-point: always the plain (unsharded) handle."""
     h = self._handle()
     points = h.project(self.param_vec)
     _, valid = h.reprojection_error(self.param_vec)
@@ -285,7 +324,8 @@ class Calibration(parameters.Parameters):
   @cached_property
   def projected(self):
     """calibration.py:113-119: projected points to each image WITHOUT the measured points (rolling shutter: the scan
-    time is iterated from the projected row, RollingFrames.max_iterations passes) -- the table the GUI draws."""
+    time is iterated from the projected row, RollingFrames.max_iterations passes) -- the table the GUI draws.  Per-point: always the
+    plain (unsharded) handle."""
     h = self._handle()
     points = h.project_model(self.param_vec, getattr(self.motion, "max_iterations", 4))
     return Table.create(points=points, valid=self.reprojected.valid)
@@ -296,20 +336,23 @@ class Calibration(parameters.Parameters):
 
   @cached_property
   def reprojection_error(self):
+    """per-point errors of the valid points; always the plain (unsharded) handle"""
     err, mask = self._errors()
     return err[mask]
 
   @cached_property
   def reprojection_inliers(self):
+    """per-point errors of the inliers; always the plain (unsharded) handle"""
     err, mask = self._errors()
     # calibration.py:138-141: point_table with valid := inliers, masked with reprojected.valid
     return err[self.reprojected.valid & choose(self.inliers, self.valid)]
 
   def residuals(self, param_vec=None):
-    """`evaluate` of calibration.py:204-206."""
+    """`evaluate` of calibration.py:204-206; always the plain (unsharded) handle."""
     return self._handle().residuals(self.param_vec if param_vec is None else param_vec)
 
   def jacobian(self, param_vec=None):
+    """always the plain (unsharded) handle"""
     return self._handle().jacobian(self.param_vec if param_vec is None else param_vec)
 
   # --- solve (calibration.py:199-212) -----------------------------------------------------------------------
@@ -320,17 +363,21 @@ class Calibration(parameters.Parameters):
     Keeps the reference's signature and semantics.  solver = "lsmr" (default, see `set_solver`) / "native" (mcba_solve): the iteration
     table scipy prints with verbose=2 is emitted in the same format through the "calibration" logger (calibration.py:208,
     io/logging.py:53-68).  solver = "scipy": the reference's own `least_squares` call on the device residuals + analytic
-    Jacobian (`Handle.solve_scipy`), scipy's own table redirected to the logger exactly as calibration.py:208 does."""
+    Jacobian (`Handle.solve_scipy`), scipy's own table redirected to the logger exactly as calibration.py:208 does.
+    Under multical_amd.distributed.sharding the "lsmr" / "native" solves run on frame-sharded handles (every rank returns the same
+    parameter vector); "scipy" stays unsharded."""
     solver = get_solver() if solver is None else solver
     if solver not in SOLVERS:
       raise ValueError(f"unknown solver {solver!r}, options are {SOLVERS}")
-    h = self._handle()
     if solver == "scipy":
+      _note_scipy_unsharded()
+      h = self._handle()
       with contextlib.redirect_stdout(LogWriter.info()):
         res = h.solve_scipy(self.param_vec, tolerance=tolerance, f_scale=f_scale, max_iterations=max_iterations, loss=loss,
                             verbose=2)
       out = self.with_param_vec(res.x)
       return (out, res) if return_result else out
+    h = self._handle(sharded=True)
     rows = []
 
     def log_row(it, nfev, cost, red, step, opt):
@@ -369,16 +416,16 @@ class Calibration(parameters.Parameters):
         hit = [v for qq, v in zip(stats[0], stats[1].quantiles) if qq == selector.quantile]
         if hit:
           return float(hit[0]) * selector.factor
-      _, _, q, _ = self._handle().error_stats(self.param_vec, quantiles=[selector.quantile])
+      _, _, q, _ = self._handle(sharded=True).error_stats(self.param_vec, quantiles=[selector.quantile])
       return float(q[0]) * selector.factor
     return selector(self.reprojection_error)
 
   def reject_outliers(self, threshold):
-    """calibration.py:240-252, evaluated on the device; only the new mask (uint8) comes back."""
-    h = self._handle()
+    """calibration.py:240-252, evaluated on the device; only the new mask (uint8) comes back (complete on every rank when sharded)."""
+    h = self._handle(sharded=True)
     try:
       n_in, n_valid = h.reject_outliers(self.param_vec, threshold)
-      inliers = h.get_inliers()
+      inliers = h.gather_inliers()
     except BaseException:
       handle_cache.invalidate_inliers(h)
       raise
@@ -393,7 +440,7 @@ class Calibration(parameters.Parameters):
   def _adjust_outliers_in_one_call(self, num_adjustments, select_scale, select_outliers, kwargs):
     """The whole loop inside the library (mcba_adjust_outliers): no Calibration objects, no re-lowering and no rotation-vector <->
     matrix round trips between the rounds.  The log lines are the reference's, emitted afterwards in the reference's order."""
-    h = self._handle()
+    h = self._handle(sharded=True)
     rows = []
 
     def log_row(it, nfev, cost, red, step, opt):
@@ -479,7 +526,7 @@ class Calibration(parameters.Parameters):
       kept = self.__dict__.get("_overall_stats")
       if kept is not None and kept[0] == key:
         return kept[1]
-    mse, rms, q, n = self._handle().error_stats(self.param_vec, quantiles=quantiles, inliers_only=inliers_only)
+    mse, rms, q, n = self._handle(sharded=True).error_stats(self.param_vec, quantiles=quantiles, inliers_only=inliers_only)
     out = struct(mse=mse, rms=rms, quantiles=q, n=n)
     if not inliers_only:
       self.__dict__["_overall_stats"] = (key, out)

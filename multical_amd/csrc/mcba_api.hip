@@ -383,6 +383,7 @@ struct mcba_handle_s {
   // outputs staging
   DevBuf<double> out_r, out_big;
   DevBuf<uint8_t> out_valid;
+  DevBuf<double> mask_words;         // mcba_gather_inliers: the reference-order mask, 32 bits per double
   DevBuf<int32_t> out_cols;
 
   // ragged camera blocks (mcba_problem.camera_n_dist): maps between the caller's parameter vector and the padded one
@@ -484,6 +485,7 @@ void scan_views(mcba_handle_s* h) {
 // The residual ordering (obs_index) is rebuilt lazily by ensure_obs_index.
 void build_inliers(mcba_handle_s* h, const uint8_t* mask_ref) {
   const Dims& d = h->d;
+  h->obs_index_dirty = true; h->compact_dirty = true;   // (first: a failure below must not leave tables marked current)
   if (d.views() > 0) {
     if (mask_ref != nullptr) {
       if (h->raw_mask.n < (size_t)d.slots()) h->raw_mask.alloc((size_t)d.slots(), false);
@@ -500,7 +502,6 @@ void build_inliers(mcba_handle_s* h, const uint8_t* mask_ref) {
   refresh_active_views(h);
   scan_views(h);
   h->out_r.alloc((size_t)std::max<int64_t>(2 * h->n_inliers, 1), false);
-  h->obs_index_dirty = true; h->compact_dirty = true;
 }
 
 void set_loss(mcba_handle_s* h, const mcba_options* opt) {
@@ -1036,33 +1037,22 @@ void select_ranks_multi(mcba_handle_s* h, const uint8_t* m2, int nsel, const lon
   }
   hipLaunchKernelGGL(k_selm_next, dim3(SEL_NEXT_BLOCKS), dim3(256), 0, h->stream, h->err_fm.p, h->evalid.p, m2, n, st, nsel,
                      dout);
-  std::vector<unsigned long long> host(3 * SEL_MAX + (size_t)SEL_NEXT_BLOCKS * SEL_MAX * 2);
-  HIP_OK(hipMemcpyAsync(host.data(), h->sel_state.p, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                        h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
+  // the tail stays on the device: the per-block partials are folded into this rank's block of ONE [W][nsel][2] message, summed over
+  // the ranks (sharded handles), folded over the ranks; one copy of the 2 nsel results and one synchronisation per batch
+  const int W = h->allreduce ? d.shard_world : 1, rank = h->allreduce ? d.shard_rank : 0;
+  REQUIRE(W >= 1 && W <= SHARD_MAX_WORLD && rank >= 0 && rank < W, "frame-sharded handle without a rank: call mcba_set_shard_rank");
+  double* msg = h->sel_f64.p;                                   // (the histogram passes are done with it)
+  double* res = h->sel_f64.p + (size_t)2 * SEL_MAX * SHARD_MAX_WORLD;
+  static_assert(2 * SEL_MAX * SHARD_MAX_WORLD + 2 * SEL_MAX <= SEL_MAX * 2048, "sel_f64 holds the tail message and its result");
+  hipLaunchKernelGGL(k_selm_fold, dim3(1), dim3(64), 0, h->stream, dout, SEL_NEXT_BLOCKS, nsel, rank, W, msg);
+  call_allreduce(h, msg, (size_t)2 * nsel * W, 0);
+  hipLaunchKernelGGL(k_selm_finish, dim3(1), dim3(64), 0, h->stream, msg, nsel, W, st, dranks, res);
+  double host[2 * SEL_MAX];
+  HIP_OK(hipMemcpyAsync(host, res, (size_t)2 * nsel * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  sync(h);
   for (int r = 0; r < nsel; ++r) {
-    double vk, next;
-    memcpy(&vk, &host[2 * r], 8);                       // SelState r: prefix = bit pattern of the order statistic
-    unsigned long long cnt = 0, mn = 0x7FF0000000000000ull;
-    for (int blk = 0; blk < SEL_NEXT_BLOCKS; ++blk) {
-      const unsigned long long* pp = &host[3 * SEL_MAX + ((size_t)blk * SEL_MAX + r) * 2];
-      cnt += pp[0];
-      mn = pp[1] < mn ? pp[1] : mn;
-    }
-    memcpy(&next, &mn, 8);
-    double cnt_le = (double)cnt;
-    if (h->allreduce) {   // combine (count, min) across ranks: sum and -max(-x)
-      double buf[2] = {cnt_le, -next};
-      HIP_OK(hipMemcpyAsync(h->sel_f64.p, buf, sizeof(buf), hipMemcpyHostToDevice, h->stream));
-      call_allreduce(h, h->sel_f64.p, 1, 0);
-      call_allreduce(h, h->sel_f64.p + 1, 1, 1);
-      HIP_OK(hipMemcpyAsync(buf, h->sel_f64.p, sizeof(buf), hipMemcpyDeviceToHost, h->stream));
-      HIP_OK(hipStreamSynchronize(h->stream));
-      cnt_le = buf[0];
-      next = -buf[1];
-    }
-    v_k[r] = vk;
-    v_k1[r] = (cnt_le > (double)(ranks[r] + 1)) ? vk : next;
+    v_k[r] = host[2 * r];
+    v_k1[r] = host[2 * r + 1];
   }
 }
 
@@ -3220,7 +3210,41 @@ int32_t mcba_solve(mcba_handle h, double* x_inout, const mcba_options* opt, mcba
  * n = number of masked points, sum_sq = sum of squared errors, values[i] = exact order statistic of rank ranks[i]
  * (0-based, ascending) found by radix select -- the inputs numpy.quantile needs (calibration.py:37-40,304-310).       */
 namespace {
-// inlier_sums (may be null; single handles with n_ranks > 0 only): {sum of squares, count} of the INLIERS as well, from the same
+// the handle's inlier table in the reference's [C,F,B,P] order (frames of other shards are zero)
+void inliers_to_host(mcba_handle h, uint8_t* mask) {
+  const Dims& d = h->d;
+  const size_t nref = (size_t)d.C * d.F * d.B * d.P;
+  h->out_valid.alloc(nref, true);
+  hipLaunchKernelGGL(k_inliers_to_ref, dim3(std::max(1, std::min(4096, (d.slots() + 255) / 256))), dim3(256), 0, h->stream, d,
+                     h->inlier.p, h->out_valid.p);
+  HIP_OK(hipMemcpyAsync(mask, h->out_valid.p, nref, hipMemcpyDeviceToHost, h->stream));
+  sync(h);
+}
+
+// ... complete on every rank of a sharded problem: this shard's bits packed 32 per double (k_pack_inliers), ONE sum over the ranks
+// of ceil(C F B P / 32) doubles, unpacked on the device, one copy down
+void gather_inliers(mcba_handle h, uint8_t* mask) {
+  if (!h->allreduce) {
+    inliers_to_host(h, mask);
+    return;
+  }
+  const Dims& d = h->d;
+  const long long nref = (long long)d.C * d.F * d.B * d.P, nwords = (nref + 31) / 32;
+  h->mask_words.alloc((size_t)std::max(nwords, 1LL), false);
+  h->out_valid.alloc((size_t)std::max(nref, 1LL), false);
+  if (nwords > 0)
+    hipLaunchKernelGGL(k_pack_inliers, dim3((unsigned)std::max(1LL, std::min(4096LL, (nwords + 255) / 256))), dim3(256), 0, h->stream, d,
+                       h->inlier.p, h->mask_words.p, nwords);
+  call_allreduce(h, h->mask_words.p, (size_t)nwords, 0);
+  if (nref > 0) {
+    hipLaunchKernelGGL(k_unpack_inliers, dim3((unsigned)std::max(1LL, std::min(4096LL, (nref + 255) / 256))), dim3(256), 0, h->stream,
+                       h->mask_words.p, nref, h->out_valid.p);
+    HIP_OK(hipMemcpyAsync(mask, h->out_valid.p, (size_t)nref, hipMemcpyDeviceToHost, h->stream));
+  }
+  sync(h);
+}
+
+// inlier_sums (may be null; n_ranks > 0 over all points only): {sum of squares, count} of the INLIERS as well, from the same
 // error pass and behind the same synchronisation (the report of the outlier loop asks for both: mcba_adjust_outliers)
 void error_stats_impl(mcba_handle h, const double* x, int32_t inliers_only, int32_t n_ranks, const int64_t* ranks,
                       double* values, int64_t* n_out, double* sum_sq, double* inlier_sums) {
@@ -3234,10 +3258,15 @@ void error_stats_impl(mcba_handle h, const double* x, int32_t inliers_only, int3
   if (h->costpart.n < (size_t)2 * grid) h->costpart.alloc((size_t)2 * std::max(grid, COST_BLOCKS_MAX));
   hipLaunchKernelGGL(k_err_sums, dim3(grid), dim3(256), 0, h->stream, h->err_fm.p, h->evalid.p, m2, d.slots(), h->costpart.p);
   hipLaunchKernelGGL(k_sum2, dim3(1), dim3(256), 0, h->stream, h->costpart.p, grid, h->scal.p);
-  call_allreduce(h, h->scal.p, 2, 0);
   int64_t n;
   const bool count_known = !h->allreduce;   // single handle: the counts are host-side facts (mcba_error_count)
-  REQUIRE(inlier_sums == nullptr || (count_known && n_ranks > 0), "internal: inlier sums ride with a selection on a single handle");
+  REQUIRE(inlier_sums == nullptr || (n_ranks > 0 && !inliers_only), "internal: inlier sums ride with a selection over all points");
+  if (inlier_sums != nullptr && !count_known) {   // sharded: the inlier sums ride in the same reduced scalar message
+    hipLaunchKernelGGL(k_err_sums, dim3(grid), dim3(256), 0, h->stream, h->err_fm.p, h->evalid.p, (const uint8_t*)h->inlier.p,
+                       d.slots(), h->costpart.p);
+    hipLaunchKernelGGL(k_sum2, dim3(1), dim3(256), 0, h->stream, h->costpart.p, grid, h->scal.p + 2);
+  }
+  call_allreduce(h, h->scal.p, inlier_sums != nullptr && !count_known ? 4 : 2, 0);
   if (count_known && n_ranks > 0) {
     // one synchronisation for the whole call: the sums come down behind the selection passes
     n = inliers_only ? h->n_inliers : h->n_evalid;
@@ -3248,7 +3277,7 @@ void error_stats_impl(mcba_handle h, const double* x, int32_t inliers_only, int3
     }
     HIP_OK(hipMemcpyAsync(h->h_scal, h->scal.p, 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   } else {
-    fetch_scalars(h, 2);
+    fetch_scalars(h, inlier_sums != nullptr ? 4 : 2);
     n = (int64_t)h->h_scal[1];
   }
   // consecutive ranks (floor / ceil of a virtual index) share one selection; all selections of a batch share the six
@@ -3315,7 +3344,7 @@ int32_t error_stats_with_quantiles(mcba_handle h, const double* x, int inliers_o
     gamma[i] = virt - fl;
   }
   double isums[2] = {0.0, 0.0};
-  const bool with_inl = inl_out != nullptr && !h->allreduce;
+  const bool with_inl = inl_out != nullptr;
   try {
     error_stats_impl(h, x, inliers_only, (int32_t)ranks.size(), ranks.data(), vals.data(), &n, &ssq, with_inl ? isums : nullptr);
   } catch (const std::exception& e) {
@@ -3403,9 +3432,7 @@ int32_t mcba_adjust_outliers(mcba_handle h, double* x_inout, const mcba_options*
   memset(&rounds[num_adjustments], 0, sizeof(mcba_round_report));
   if (int32_t rc = report(rounds[num_adjustments])) return rc;
   lap("report", num_adjustments);
-  if (inliers_out) {
-    if (int32_t rc = mcba_get_inliers(h, inliers_out)) return rc;
-  }
+  if (inliers_out) gather_inliers(h, inliers_out);   // (the complete mask on every rank of a sharded problem)
   API_END
 }
 
@@ -3426,6 +3453,9 @@ int32_t mcba_reject_outliers(mcba_handle h, const double* x, double threshold, i
   g_fill_stream = h->stream;
   const Dims& d = h->d;
   compute_errors(h, x);
+  // the inlier table changes from here on: mark what depends on it stale first (a failure below must not leave them marked current)
+  h->obs_index_dirty = true; h->compact_dirty = true;
+  h->view_first_dirty = true;
   if (d.views() > 0)
     hipLaunchKernelGGL(k_reject, dim3(d.views()), dim3(64), 0, h->stream, d, h->err_fm.p, h->evalid.p, threshold, h->inlier.p,
                        h->view_count.p);
@@ -3438,19 +3468,14 @@ int32_t mcba_reject_outliers(mcba_handle h, const double* x, double threshold, i
   hipLaunchKernelGGL(k_err_sums, dim3(grid), dim3(256), 0, h->stream, h->err_fm.p, h->evalid.p, (const uint8_t*)nullptr,
                      d.slots(), h->costpart.p);
   hipLaunchKernelGGL(k_sum2, dim3(1), dim3(256), 0, h->stream, h->costpart.p, grid, h->scal.p + 2);
-  fetch_scalars(h, 4);
-  h->n_inliers = (int64_t)h->h_scal[1];      // this shard's inliers
-  h->obs_index_dirty = true; h->compact_dirty = true;
-  h->view_first_dirty = true;
-  h->out_r.alloc((size_t)std::max<int64_t>(2 * h->n_inliers, 1), false);
-  double tot[2] = {h->h_scal[1], h->h_scal[3]};
-  if (h->allreduce) {
-    HIP_OK(hipMemcpyAsync(h->scal.p, tot, sizeof(tot), hipMemcpyHostToDevice, h->stream));
-    call_allreduce(h, h->scal.p, 2, 0);
-    fetch_scalars(h, 2);
-    tot[0] = h->h_scal[0];
-    tot[1] = h->h_scal[1];
+  if (h->allreduce) {   // the shard totals {inliers, valid} reduced where they are: scal[4, 6), one fetch behind the sum
+    hipLaunchKernelGGL(k_pair, dim3(1), dim3(64), 0, h->stream, h->scal.p + 1, h->scal.p + 3, h->scal.p + 4);
+    call_allreduce(h, h->scal.p + 4, 2, 0);
   }
+  fetch_scalars(h, h->allreduce ? 6 : 4);
+  h->n_inliers = (int64_t)h->h_scal[1];      // this shard's inliers
+  h->out_r.alloc((size_t)std::max<int64_t>(2 * h->n_inliers, 1), false);
+  const double tot[2] = {h->h_scal[h->allreduce ? 4 : 1], h->h_scal[h->allreduce ? 5 : 3]};
   if (n_inliers) *n_inliers = (int64_t)tot[0];
   if (n_valid) *n_valid = (int64_t)tot[1];
   API_END
@@ -3461,13 +3486,16 @@ int32_t mcba_get_inliers(mcba_handle h, uint8_t* mask) {
   API_BEGIN
   REQUIRE(h && mask, "null argument");
   g_fill_stream = h->stream;
-  const Dims& d = h->d;
-  const size_t nref = (size_t)d.C * d.F * d.B * d.P;
-  h->out_valid.alloc(nref, true);
-  hipLaunchKernelGGL(k_inliers_to_ref, dim3(std::max(1, std::min(4096, (d.slots() + 255) / 256))), dim3(256), 0, h->stream, d,
-                     h->inlier.p, h->out_valid.p);
-  HIP_OK(hipMemcpyAsync(mask, h->out_valid.p, nref, hipMemcpyDeviceToHost, h->stream));
-  sync(h);
+  inliers_to_host(h, mask);
+  API_END
+}
+
+/* the complete inlier table on every rank of a frame-sharded problem (one collective); mcba_get_inliers on a single handle  */
+int32_t mcba_gather_inliers(mcba_handle h, uint8_t* mask) {
+  API_BEGIN
+  REQUIRE(h && mask, "null argument");
+  g_fill_stream = h->stream;
+  gather_inliers(h, mask);
   API_END
 }
 

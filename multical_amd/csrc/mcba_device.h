@@ -81,6 +81,13 @@ struct Dims {
     const int q = i - off_motion, f = (q >= 6 * F ? q - 6 * F : q) / 6;
     return (f >= f0 && f < f0 + Fl) ? 1.0 : 0.0;
   }
+  // frame-major slot of this shard that holds entry i of a reference-order [C,F,B,P] table; -1 for a frame of another shard
+  MCBA_HD long long ref_to_slot(long long i) const {
+    const long long bp = (long long)B * P, fbp = (long long)F * bp;
+    const long long c = i / fbp, f = (i - c * fbp) / bp, r = i - c * fbp - f * bp;
+    if (f < f0 || f >= f0 + Fl) return -1;
+    return ((f - f0) * C + c) * bp + r;
+  }
   MCBA_HD int views() const { return Fl * C * B; }
   MCBA_HD int slots() const { return Fl * C * B * P; }
   MCBA_HD int view_stride() const { return VIEW_STRIDE * (motion == MOTION_ROLLING ? 2 : 1); }

@@ -3245,6 +3245,90 @@ __global__ __launch_bounds__(256) void k_selm_next(const double* __restrict__ er
   }
 }
 
+// tail of the selection without the host: this rank's {count <= v_r, smallest element > v_r} over the k_selm_next partials, as
+// block `rank` of a [world][nsel][2] message gathered by summation (every other block zero; the bit pattern travels as the
+// double it is -- adding zeros keeps it exact).  One wave.
+__global__ __launch_bounds__(64) void k_selm_fold(const unsigned long long* __restrict__ part, int nblk, int nsel, int rank, int world,
+                                                  double* __restrict__ msg) {
+  const int lane = threadIdx.x;
+  unsigned long long cnt[SEL_MAX], mn[SEL_MAX];
+#pragma unroll
+  for (int r = 0; r < SEL_MAX; ++r) {
+    cnt[r] = 0;
+    mn[r] = 0x7FF0000000000000ull;   // +inf
+  }
+  for (int b = lane; b < nblk; b += 64)
+#pragma unroll
+    for (int r = 0; r < SEL_MAX; ++r)
+      if (r < nsel) {
+        cnt[r] += part[((size_t)b * SEL_MAX + r) * 2];
+        const unsigned long long m = part[((size_t)b * SEL_MAX + r) * 2 + 1];
+        mn[r] = m < mn[r] ? m : mn[r];
+      }
+#pragma unroll
+  for (int r = 0; r < SEL_MAX; ++r) {
+    for (int off = 32; off > 0; off >>= 1) {
+      cnt[r] += __shfl_down(cnt[r], off, 64);
+      const unsigned long long o = __shfl_down(mn[r], off, 64);
+      mn[r] = o < mn[r] ? o : mn[r];
+    }
+    cnt[r] = __shfl(cnt[r], 0, 64);
+    mn[r] = __shfl(mn[r], 0, 64);
+  }
+  for (int e = lane; e < 2 * nsel * world; e += 64) {   // (every entry written once, by one lane)
+    const int w = e / (2 * nsel), r = (e >> 1) % nsel;
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < SEL_MAX; ++k)
+      if (k == r && w == rank) v = (e & 1) ? __longlong_as_double((long long)mn[k]) : (double)cnt[k];
+    msg[e] = v;
+  }
+}
+// ... and the gathered message folded over the ranks: out[2 r] = v_r (the selected order statistic), out[2 r + 1] = the next one
+// in ascending order (v_r itself when more than rank + 1 elements are <= v_r).  Counts are integers below 2^53 (exact sums),
+// the minimum is taken over the bit patterns after the gather.
+__global__ __launch_bounds__(64) void k_selm_finish(const double* __restrict__ msg, int nsel, int world, const SelState* __restrict__ st,
+                                                    const long long* __restrict__ ranks, double* __restrict__ out) {
+  const int r = threadIdx.x;
+  if (r >= nsel) return;
+  double cnt = 0.0;
+  unsigned long long mn = 0x7FF0000000000000ull;
+  for (int w = 0; w < world; ++w) {
+    cnt += msg[(w * nsel + r) * 2];
+    const unsigned long long m = (unsigned long long)__double_as_longlong(msg[(w * nsel + r) * 2 + 1]);
+    mn = m < mn ? m : mn;
+  }
+  const double vk = __longlong_as_double((long long)st[r].prefix);
+  out[2 * r] = vk;
+  out[2 * r + 1] = cnt > (double)(ranks[r] + 1) ? vk : __longlong_as_double((long long)mn);
+}
+
+// ---- complete inlier mask of a frame-sharded problem (mcba_gather_inliers) --------------------------------------------------------
+// word w holds entries [32 w, 32 w + 32) of the reference-order [C,F,B,P] mask as the integer value of a double; this rank sets
+// the bits of its own frames only, so ONE sum over the ranks ORs the shards (disjoint bits: every word sums to an integer below
+// 2^32, exact in a double) -- also for a word that straddles a shard boundary.  Every word is written (zeros included).
+__global__ void k_pack_inliers(Dims d, const uint8_t* __restrict__ inlier, double* __restrict__ words, long long nwords) {
+  const long long nref = (long long)d.C * d.F * d.B * d.P;
+  for (long long w = blockIdx.x * (long long)blockDim.x + threadIdx.x; w < nwords; w += (long long)gridDim.x * blockDim.x) {
+    unsigned int bits = 0u;
+    const long long i0 = 32 * w, i1 = i0 + 32 < nref ? i0 + 32 : nref;
+    for (long long i = i0; i < i1; ++i) {
+      const long long s = d.ref_to_slot(i);
+      if (s >= 0 && inlier[s]) bits |= 1u << (int)(i - i0);
+    }
+    words[w] = (double)bits;
+  }
+}
+__global__ void k_unpack_inliers(const double* __restrict__ words, long long nref, uint8_t* __restrict__ out) {
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nref; i += (long long)gridDim.x * blockDim.x)
+    out[i] = (uint8_t)(((unsigned int)words[i >> 5] >> (int)(i & 31)) & 1u);
+}
+// out = {a[0], b[0]}: the shard totals {inliers, valid points} of mcba_reject_outliers as one 2-double message
+__global__ void k_pair(const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out) {
+  if (threadIdx.x == 0) out[0] = a[0];
+  if (threadIdx.x == 1) out[1] = b[0];
+}
+
 __global__ void k_u32_to_f64(const unsigned int* __restrict__ in, double* __restrict__ out, int n) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = (double)in[i];
 }

@@ -116,16 +116,17 @@ def init_native_allreduce(h, rank, world_size, group=None):
   return True
 
 
-def sharded_handle(calib, rank=None, world_size=None, group=None, balance=True, native=None, shards=None):
+def sharded_handle(calib, rank=None, world_size=None, group=None, balance=True, native=None, shards=None, problem=None):
   """Handle owning this rank's frame shard.  Reductions: the library's own RCCL communicator (`native`, default when the
   group's backend is nccl, i.e. one GPU per rank) or a torch.distributed hook (gloo tests, fallback).
-  `shards`: explicit [(f0, f1)] * world_size instead of the balanced plan (empty ranges are legal)."""
+  `shards`: explicit [(f0, f1)] * world_size instead of the balanced plan (empty ranges are legal).
+  `problem`: lower(calib) when the caller already has it."""
   import torch
   import torch.distributed as dist
   from .backend import Handle, lower
   rank = dist.get_rank(group) if rank is None else rank
   world_size = dist.get_world_size(group) if world_size is None else world_size
-  prob = lower(calib)
+  prob = lower(calib) if problem is None else problem
   weights = None
   if balance:
     inl = calib.inliers
@@ -145,3 +146,97 @@ def sharded_handle(calib, rank=None, world_size=None, group=None, balance=True, 
     h.set_shard_rank(rank, world_size)
   h.frame_range = shards[rank]
   return h
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# opt-in sharding of the drop-in API: multical_amd.Calibration (and through it Workspace.calibrate) runs its solves and outlier
+# loops on frame-sharded handles while a `sharding()` block is active.  Off by default -- a process group alone changes nothing.
+# ---------------------------------------------------------------------------------------------------------------------
+_sharding = {"on": False, "group": None, "native": None, "balance": True}
+
+
+def _require_group(group):
+  try:
+    import torch.distributed as dist
+  except Exception as e:   # pragma: no cover - torch without distributed support
+    raise RuntimeError("multical_amd sharding needs torch.distributed") from e
+  if not (dist.is_available() and dist.is_initialized()):
+    raise RuntimeError("multical_amd sharding needs an initialised torch.distributed process group "
+                       "(torch.distributed.init_process_group, e.g. under torchrun) before it is turned on")
+  return dist.get_world_size(group)
+
+
+def enable_sharding(group=None, native=None, balance=True):
+  """Turn frame sharding on for the solves and outlier loops of multical_amd.Calibration over `group` (default: the default
+  process group).  `native` / `balance` as in `sharded_handle`.  Every rank of the group must make the same calls."""
+  _require_group(group)
+  _sharding.update(on=True, group=group, native=native, balance=bool(balance))
+
+
+def disable_sharding():
+  """Turn sharding off and close the sharded handles of the group (collective-free: each rank releases its own)."""
+  group, was_on = _sharding["group"], _sharding["on"]
+  _sharding.update(on=False, group=None, native=None, balance=True)
+  if was_on:
+    from .calibration import handle_cache
+    handle_cache.close_sharded(group)
+
+
+def sharding_enabled():
+  return _sharding["on"]
+
+
+class sharding(object):
+  """with multical_amd.distributed.sharding(): ... -- enable_sharding(...) for the block, the previous state afterwards."""
+
+  def __init__(self, group=None, native=None, balance=True):
+    self.args = (group, native, balance)
+
+  def __enter__(self):
+    self.prev = dict(_sharding)
+    enable_sharding(*self.args)
+    return self
+
+  def __exit__(self, *exc):
+    disable_sharding()
+    if self.prev["on"]:
+      _sharding.update(self.prev)
+    return False
+
+
+def shard_config():
+  """(group, world_size, native, balance) of the active sharding, or None when it is off or the group has one rank."""
+  if not _sharding["on"]:
+    return None
+  world = _require_group(_sharding["group"])
+  if world <= 1:
+    return None
+  return _sharding["group"], world, _sharding["native"], _sharding["balance"]
+
+
+def shard_plan(calib, world_size, balance=True):
+  """The frame shards `sharded_handle` uses: frame_shards(F, W, inliers per frame) -- from replicated inputs, so every rank
+  computes the same plan.  None for one rank."""
+  if world_size <= 1:
+    return None
+  F = calib.point_table.valid.shape[1]
+  weights = calib.inliers.sum(axis=(0, 2, 3)).astype(np.float64) if balance else None
+  return frame_shards(F, world_size, weights)
+
+
+def agree_on_plan(shards, group=None):
+  """All-gathers the bounds of `shards` and raises on EVERY rank when any rank computed another plan (all ranks take part
+  in the one collective and then decide on the same gathered data: none is left waiting in a later collective)."""
+  import torch
+  import torch.distributed as dist
+  bounds = [shards[0][0]] + [b for _, b in shards]
+  dev = "cuda" if dist.get_backend(group) == "nccl" else "cpu"
+  mine = torch.tensor(bounds, dtype=torch.int64, device=dev)
+  world = dist.get_world_size(group)
+  got = [torch.empty_like(mine) for _ in range(world)]
+  dist.all_gather(got, mine, group=group)
+  rows = [t.cpu().tolist() for t in got]
+  if any(r != rows[0] for r in rows):
+    raise RuntimeError(f"frame-shard plans differ across the ranks: {rows} -- the Calibration (its point table or inlier "
+                       f"mask) is not the same on every rank")
+  return shards

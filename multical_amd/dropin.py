@@ -16,12 +16,19 @@ and `HandEyeCalibration.bundle_adjust` (optimization/hand_eye.py:73-75) reach th
 `bundle_adjust` keeps the reference's signature, returns `self.with_param_vec(res.x)` exactly like the reference, does
 not mutate `self`, stores nothing on the Calibration (pickling is unaffected, calibration.py:222-226) and writes the
 scipy-style iteration table to the same "calibration" logger.  See INTEGRATION.md.
+
+    dropin.install(shard=True)      # (or MULTICAL_SHARD=1) under torchrun: every rank solves its frame shard and returns the same
+                                    # Calibration; off by default, a process group alone changes nothing
 """
 import os
 
 import numpy as np
 
+from . import distributed
 from .backend import Handle, lower
+
+# install(shard=True): bundle_adjust runs on a frame-sharded handle over `group` (default process group) when it has > 1 rank
+_shard = {"on": False, "group": None, "native": None}
 
 _HEADER = "{:^15}{:^15}{:^15}{:^15}{:^15}{:^15}".format("Iteration", "Total nfev", "Cost", "Cost reduction", "Step norm",
                                                         "Optimality")
@@ -47,11 +54,28 @@ def bundle_adjust_native(self, tolerance=1e-4, f_scale=1.0, max_iterations=100, 
   return _bundle_adjust_device(self, tolerance, f_scale, max_iterations, loss, 'exact')
 
 
+def _device_handle(self):
+  """Handle for one bundle_adjust: frame-sharded over the install(shard=True) group -- or the group of an active
+  multical_amd.distributed.sharding() -- when it has more than one rank, else plain."""
+  cfg = None
+  if _shard["on"]:
+    world = distributed._require_group(_shard["group"])
+    cfg = (_shard["group"], world, _shard["native"], True) if world > 1 else None
+  else:
+    cfg = distributed.shard_config()
+  if cfg is not None:
+    group, world, native, balance = cfg
+    prob = lower(self)
+    plan = distributed.agree_on_plan(distributed.shard_plan(self, world, balance), group)
+    return distributed.sharded_handle(self, group=group, native=native, shards=plan, problem=prob)
+  return Handle(lower(self))
+
+
 def _bundle_adjust_device(self, tolerance, f_scale, max_iterations, loss, _tr_solver):
   import logging
   log = logging.getLogger("calibration")        # multical/io/logging.py:11
   rows = []
-  with Handle(lower(self)) as h:
+  with _device_handle(self) as h:
     h.set_log(lambda *a: rows.append(_format_row(*a)))
     res = h.solve(self.param_vec, tolerance=tolerance, f_scale=f_scale, max_iterations=max_iterations, loss=loss,
                   tr_solver=_tr_solver)
@@ -89,20 +113,29 @@ MODES = {"lsmr": bundle_adjust, "native": bundle_adjust_native, "scipy": bundle_
 
 
 def _reprojection_tables(self):
-  """(errors, mask) of tables.reprojection_error(self.reprojected, self.point_table) on the device (tables.py:244-249)."""
+  """(errors, mask) of tables.reprojection_error(self.reprojected, self.point_table) on the device (tables.py:244-249).  Per-point:
+  always a plain (unsharded) handle, also after install(shard=True)."""
   with Handle(lower(self)) as h:
     return h.reprojection_error(self.param_vec)
 
 
-def install(calibration_module=None, patch_errors=False, mode="lsmr"):
+def install(calibration_module=None, patch_errors=False, mode="lsmr", shard=False, group=None, native=None):
   """Patch `Calibration.bundle_adjust` of multical (or of the given module object).  Returns the patched class.
   mode = "lsmr" (default): mcba_solve with scipy's TRF + LSMR step on the device -- the reference's end point.
   mode = "native": mcba_solve with exact steps (fastest; the converged optimum, not the reference's end point).
   mode = "scipy": the reference's own scipy driver on the device residuals + analytic Jacobian (host-side LSMR).
-  patch_errors=True additionally evaluates `reprojection_error` / `reject_outliers` on the device."""
+  patch_errors=True additionally evaluates `reprojection_error` / `reject_outliers` on the device.
+  shard=True: bundle_adjust ("lsmr" / "native") solves on a frame-sharded handle over `group` (default: the default process group,
+  which must be initialised by the time bundle_adjust runs) when the group has more than one rank; every rank returns the same
+  Calibration.  `native`: the library's own RCCL communicator (default with the nccl backend).  "scipy" stays unsharded."""
   if mode not in MODES:
     raise ValueError(f"unknown mode {mode!r}, options are {sorted(MODES)}")
   import logging
+  _shard.update(on=bool(shard), group=group, native=native)
+  if shard:
+    logging.getLogger("calibration").info(
+      "multical_amd: bundle_adjust frame-sharded across the ranks of the process group%s",
+      " (not for solver 'scipy': every rank solves the whole rig)" if mode == "scipy" else "")
   logging.getLogger("calibration").info(
     "multical_amd: Calibration.bundle_adjust -> HIP back-end, solver '%s' (%s)", mode,
     {"lsmr": "scipy's TRF + LSMR steps restated on the device: the reference's end point; ~100x the time of 'native'",
@@ -134,16 +167,19 @@ def uninstall(calibration_module=None):
   if hasattr(cls, "_scipy_bundle_adjust"):
     cls.bundle_adjust = cls._scipy_bundle_adjust
     del cls._scipy_bundle_adjust
+  _shard.update(on=False, group=None, native=None)
 
 
 def install_from_env():
   """MULTICAL_BACKEND=hip (or hip-lsmr) -> install(): the reference's end point on the device; hip-native -> install(mode="native");
-  hip-scipy -> install(mode="scipy"); anything else keeps the reference's scipy path untouched."""
+  hip-scipy -> install(mode="scipy"); anything else keeps the reference's scipy path untouched.
+  MULTICAL_SHARD=1 beside a hip back-end -> install(..., shard=True): frame-sharded over the default process group (torchrun)."""
   backend = os.environ.get("MULTICAL_BACKEND", "scipy").lower().replace("_", "-")
+  shard = os.environ.get("MULTICAL_SHARD", "0").strip().lower() in ("1", "true", "yes", "on")
   if backend in ("hip", "hip-lsmr"):
-    return install()
+    return install(shard=shard)
   if backend == "hip-native":
-    return install(mode="native")
+    return install(mode="native", shard=shard)
   if backend == "hip-scipy":
-    return install(mode="scipy")
+    return install(mode="scipy", shard=shard)
   return None
