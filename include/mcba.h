@@ -288,6 +288,34 @@ int32_t mcba_synchronize(mcba_handle h);
 /* dense J^T J [n_params x n_params] assembled from the block form (debug / parity tests; small problems only)  */
 int32_t mcba_dense_hessian(mcba_handle h, double* H);
 
+/* --- parameter covariance ------------------------------------------------------------------- */
+/* Gauss-Newton covariance of x at x:  Sigma = sigma2 (J^T J)^-1 over the FREE parameters, with J the Jacobian of the LINEAR
+ * loss over the current inliers (exactly mcba_jacobian's).  Not part of the reference (its bundle_adjust reports no
+ * uncertainty); the counterpart of the standard deviations cv2.calibrateCameraExtended returns for intrinsics.
+ *   - free = not held and observed.  hold: [n_params] uint8 in the caller's x order, 1 = held (removed from the system; its
+ *     rows and columns of Sigma are 0, std 0), or NULL = none held.  The problem has a 12-dimensional gauge freedom (camera
+ *     poses x rig poses, rig poses x board poses): the caller holds it (multical_amd.gauge.default_hold), or the call fails.
+ *   - unobserved: diag(J^T J) == 0 exactly (invalid frames / cameras / boards, frozen intrinsic columns, a skew no residual
+ *     depends on).  Excluded from the system and from p_free; std NaN, covariance 0.
+ *   - sigma2 <= 0: estimated as |r|^2 / (m - p_free), m = n_residuals; m <= p_free is an error.  *sigma2_out receives the
+ *     value used, *dof_out = m - p_free.
+ *   - rank deficiency: the system is factored in the Jacobi-scaled space (D = diag(J^T J)^-1/2, unit diagonal); any
+ *     Cholesky pivot L_kk^2 < 1e-10 -- of a frame block or of the reduced system -- fails the call with a message that names
+ *     the parameter ("covariance: rank deficient at x[37] (cameras[1].cx); hold more parameters").
+ *   - outputs (any may be NULL): the per-frame motion parameters (DF = 6 static, 12 rolling shutter: start then end pose)
+ *     are eliminated; every other parameter is SHARED.
+ *       cov_shared        [n_shared, n_shared]  rows / columns in the order of shared_index (ascending caller x index)
+ *       cov_frames        [F, DF, DF]           marginal block of each frame (x indices of mcba_problem's motion block)
+ *       cov_frame_shared  [F, DF, n_shared]     cross blocks frame x shared (only computed when asked for)
+ *       std_out           [n_params]            sqrt(diag(Sigma)) in the caller's x order
+ *     Covariances between two different frames are not produced.
+ *   - single handle only (a frame-sharded handle is refused); reduced systems of at most 1023 shared parameters.
+ * The call evaluates the linear-loss normal equations at x on the handle; the solver's own state is rebuilt by every solve. */
+/* n_shared, DF and the caller-order x index of every shared parameter (shared_index: [n_shared] or NULL) */
+int32_t mcba_covariance_layout(mcba_handle h, int32_t* n_shared, int32_t* df, int32_t* shared_index);
+int32_t mcba_covariance(mcba_handle h, const double* x, const uint8_t* hold, double sigma2, double* cov_shared,
+                        double* cov_frames, double* cov_frame_shared, double* std_out, double* sigma2_out, int64_t* dof_out);
+
 /* --- initialisation tables (the producer of the hot path's inputs) ---------------------------- */
 /* matrix.align_transforms_robust (transform/matrix.py:140-153) for a batch of problems: problem p owns the pose pairs
  * [offsets[p], offsets[p+1]) of A and B (row-major 4x4 "points-transforming" matrices), `mask` (or NULL = all) selects

@@ -97,6 +97,9 @@ SYMBOLS = [
   ("mcba_normal_equations_device", C.c_int32, [H, C.POINTER(Options)]),
   ("mcba_synchronize", C.c_int32, [H]),
   ("mcba_dense_hessian", C.c_int32, [H, c_double_p]),
+  ("mcba_covariance_layout", C.c_int32, [H, c_int32_p, c_int32_p, c_int32_p]),
+  ("mcba_covariance", C.c_int32, [H, c_double_p, c_uint8_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p,
+                                  c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_solve", C.c_int32, [H, c_double_p, C.POINTER(Options), C.POINTER(Result)]),
   ("mcba_time_linearize", C.c_int32, [H, c_double_p, C.POINTER(Options), C.c_int32, c_double_p]),
   ("mcba_time_residuals", C.c_int32, [H, c_double_p, C.c_int32, c_double_p]),

@@ -309,6 +309,47 @@ class Handle(object):
     check(self.lib.mcba_dense_hessian(self.h, _ptr(H, C.c_double)))
     return H
 
+  def covariance(self, x, hold=None, sigma2=None, frames=True, cross=False):
+    """Gauss-Newton covariance sigma2 (J^T J)^-1 of the free parameters at x, linear loss over the current inliers
+    (mcba_covariance).  hold: [n_params] mask of held parameters (None = none held: the gauge must then be fixed otherwise).
+    sigma2: known residual variance, or None = |r|^2 / (m - p_free).  Returns struct(shared [n_shared, n_shared], shared_index,
+    frames [F, DF, DF] (frames=True), frame_index [F, DF], frame_shared [F, DF, n_shared] (cross=True), std [n_params]
+    (0 where held, NaN where unobserved), sigma2, dof)."""
+    from .structs import struct
+    x = self._x(x)
+    ns, df = C.c_int32(), C.c_int32()
+    check(self.lib.mcba_covariance_layout(self.h, C.byref(ns), C.byref(df), None))
+    n_shared, DF = ns.value, df.value
+    shared_index = np.empty(n_shared, dtype=np.int32)
+    check(self.lib.mcba_covariance_layout(self.h, C.byref(ns), C.byref(df), _ptr(shared_index, C.c_int32)))
+    F = int(self.shape[1])
+    hold_u8 = None
+    if hold is not None:
+      hold_u8 = _u8(np.asarray(hold).astype(bool))
+      assert hold_u8.shape == (self.n_params,), f"hold mask of length {hold_u8.size}, expected {self.n_params}"
+    shared = np.empty((n_shared, n_shared))
+    fr = np.empty((F, DF, DF)) if frames else None
+    fs = np.empty((F, DF, n_shared)) if cross else None
+    std = np.empty(self.n_params)
+    s2, dof = C.c_double(), C.c_int64()
+    opt = lambda a: None if a is None else _ptr(a, C.c_double)
+    check(self.lib.mcba_covariance(self.h, _ptr(x, C.c_double), None if hold_u8 is None else _ptr(hold_u8, C.c_uint8),
+                                   0.0 if sigma2 is None else float(sigma2), _ptr(shared, C.c_double), opt(fr), opt(fs),
+                                   _ptr(std, C.c_double), C.byref(s2), C.byref(dof)))
+    # eliminated frame parameters: the indices shared_index leaves out (static: frame-major; rolling: F start poses, then F end poses)
+    rest = np.setdiff1d(np.arange(self.n_params), shared_index)
+    if DF == 12:
+      frame_index = rest.reshape(2, F, 6).transpose(1, 0, 2).reshape(F, 12)
+    else:
+      frame_index = rest.reshape(F, DF)
+    out = struct(shared=shared, shared_index=shared_index.astype(np.int64), frame_index=frame_index, std=std,
+                 sigma2=s2.value, dof=dof.value)
+    if frames:
+      out = out._extend(frames=fr)
+    if cross:
+      out = out._extend(frame_shared=fs)
+    return out
+
   def debug_gn_step(self, reg):
     gn = np.empty(self.n_params)
     gh = np.empty(self.n_params)

@@ -542,6 +542,64 @@ class Calibration(parameters.Parameters):
     else:
       info(f"{stage} reprojection RMS={overall.rms:.3f}, n={overall.n}, quantiles={overall.quantiles}")
 
+  # --- parameter uncertainty ---------------------------------------------------------------------
+  def covariance(self, hold=None, sigma2=None, cross=False):
+    """Gauss-Newton covariance sigma2 (J^T J)^-1 of param_vec at the current parameters: linear loss over the current inliers
+    (compute it after outlier rejection).  hold: mask over param_vec of the parameters held fixed (default:
+    gauge.default_hold); sigma2: known residual variance (None: |r|^2 / (m - p_free)).  Returns struct(shared,
+    shared_index, frames [F, DF, DF], frame_index [F, DF], frame_shared [F, DF, n_shared] (cross=True), std, sigma2, dof,
+    held).  Always the plain (unsharded) handle: under sharding() every rank computes the same result."""
+    from . import gauge
+    held = gauge.default_hold(self) if hold is None else np.asarray(hold).astype(bool)
+    cov = self._handle().covariance(self.param_vec, hold=held, sigma2=sigma2, frames=True, cross=cross)
+    return cov._extend(held=held)
+
+  def parameter_std(self, hold=None, sigma2=None):
+    """Standard deviations of the parameters split like `params` (parameters.split): camera_poses [C, 6], board_poses
+    [B, 6], motion (shaped as its params), cameras (one array per camera), boards -- the enabled blocks only.  0 where held,
+    NaN where no residual depends on the parameter."""
+    from . import gauge
+    held = gauge.default_hold(self) if hold is None else np.asarray(hold).astype(bool)
+    cov = self._handle().covariance(self.param_vec, hold=held, sigma2=sigma2, frames=False)
+    return split_std(self, cov.std)
+
+  def report_uncertainty(self, stage="", hold=None):
+    """One line per camera through the "calibration" logger: standard deviations of fx, fy, cx, cy (px) and of the camera
+    pose (rotation in degrees, translation in board units) in the gauge of `hold` (default: gauge.default_hold)."""
+    std = self.parameter_std(hold=hold)
+    names = getattr(self.camera_poses, "names", None) or [f"cam{i}" for i in range(self.size.cameras)]
+    for c in range(self.size.cameras):
+      parts = [f"{stage} {names[c]}:"]
+      if "cameras" in std:
+        k = np.asarray(std["cameras"][c]).ravel()
+        parts.append(f"std fx={k[0]:.3f} fy={k[1]:.3f} cx={k[2]:.3f} cy={k[3]:.3f} px")
+      if "camera_poses" in std:
+        p = np.asarray(std["camera_poses"][c]).ravel()
+        parts.append(f"pose std rotation={np.degrees(np.linalg.norm(p[:3])):.4f} deg translation={np.linalg.norm(p[3:]):.5f}")
+      info(" ".join(parts))
+
+
+def split_std(calib, std):
+  """A vector over calib.param_vec (standard deviations) split into the enabled blocks: camera_poses [C, 6], board_poses
+  [B, 6], motion (static [F, 6]; rolling shutter [start [F, 6], end [F, 6]]; hand-eye struct(world_wrt_base [6],
+  gripper_wrt_camera [6])), cameras (one array per camera: fx fy cx cy skew dist..), boards (one [P_b, 3] array per board)."""
+  blocks = parameters.split(np.asarray(std, dtype=np.float64), calib.params)
+  out = struct()
+  for k, v in blocks.items():
+    if k in ("camera_poses", "board_poses"):
+      v = v.reshape(-1, 6)
+    elif k == "motion":
+      mp = calib.motion.params
+      v = parameters.split(v, mp)
+      if not isinstance(mp, Struct):
+        v = v.reshape(-1, 6) if isinstance(v, np.ndarray) else [a.reshape(-1, 6) for a in v]
+    elif k == "cameras":
+      v = parameters.split(v, [np.asarray(c.param_vec) for c in calib.cameras])
+    elif k == "boards":
+      v = [a.reshape(-1, 3) for a in parameters.split(v, [np.asarray(b.param_vec) for b in calib.boards])]
+    out[k] = v
+  return out
+
 
 # ---------------------------------------------------------------------------------------------------------------
 # builder from a synthetic rig (multical_amd.synthetic.make_rig)

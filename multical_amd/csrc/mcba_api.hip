@@ -32,6 +32,7 @@
 #include "mcba_camops.h"
 #include "mcba_lower.h"
 #include "mcba_solver_kernels.h"
+#include "mcba_cov_kernels.h"
 #include "mcba_init_kernels.h"
 
 using namespace mcba;
@@ -331,6 +332,10 @@ struct mcba_handle_s {
   int lsmr_fused = 2;                     // the form in force (resolved from lsmr_fused_setting by lsmr_setup)
   ScalLayout sl;
   DevBuf<double> chol_linv;   // inverted diagonal tiles of the panel kernels (k_cholp_back)
+  // mcba_covariance: D (0 = held / unobserved), zero vector (right-hand side of the reused Schur kernels), L^-1 of the reduced
+  // system, its SYRK partials, Sigma_ss scaled (padded) and unscaled, per-frame blocks and cross blocks, pivot report
+  DevBuf<double> cov_d, cov_zero, cov_x, cov_p, cov_sg, cov_sout, cov_ff, cov_fs;
+  DevBuf<int32_t> cov_bad;
   int lin_grid = 0;          // 0 = automatic (see lin2), > 0 = forced number of persistent workgroups (debug)
 
   int64_t n_inliers = 0;               // inliers of this shard
@@ -817,6 +822,25 @@ long long* g_chol_prof = nullptr;    // device buffer of 8 phase stamps (mcba_de
 //   larger           k_cholb_*      multi-workgroup 64-column panels (adjust_board with thousands of board points)
 // (The column-by-column LDS kernel of round 1, the 32-column single-workgroup kernel and the matrix-in-L2 tile kernel of
 //  round 2 lost to these at every size and are gone: profiles/r03_cholesky_paths.txt.)
+// the factor of the panel path alone (ns + 1 <= CHOLP_MAX_N1): L goes back into the lower triangle of buf, the inverted
+// diagonal tiles L_kk^-1 into h->chol_linv, the first non-positive pivot into h->info
+void launch_cholp_factor(mcba_handle_s* h, int ns, double reg, double* buf) {
+  const int nb = (ns + 1 + CT - 1) / CT, nbc = (ns + CT - 1) / CT;
+  const size_t nlinv = (size_t)nb * CT * CT;
+  if (h->chol_linv.n < nlinv) h->chol_linv.alloc(nlinv, false);
+  for (int kt0 = 0; kt0 < nbc;) {
+    const int wt = cholp_panel_tiles(ns, kt0);
+    const size_t lds = cholp_lds_bytes(ns, kt0, wt);
+    raise_dynamic_lds((const void*)k_cholp_panel, h->device, lds);
+    hipLaunchKernelGGL(k_cholp_panel, dim3(1), dim3(CHOLP_THREADS), lds, h->stream, ns, kt0, wt, reg, buf, h->chol_linv.p,
+                       h->info.p, g_chol_prof);
+    const int k1 = kt0 + wt, m = nb - k1, nt = m * (m + 1) / 2;
+    if (k1 < nbc && nt > 0)
+      hipLaunchKernelGGL(k_cholp_trail, dim3((nt + 3) / 4), dim3(256), 0, h->stream, ns, kt0, wt, buf);
+    kt0 = k1;
+  }
+}
+
 void launch_chol(mcba_handle_s* h, int ns, double reg, double* buf, double* ps) {
   if (ns + 1 <= CHOL_BLK_MAX_N1 && !g_force_blocked_chol && !g_force_panel2_chol) {
     const size_t lds_blk = chol_blk_lds_bytes(ns);
@@ -825,20 +849,7 @@ void launch_chol(mcba_handle_s* h, int ns, double reg, double* buf, double* ps) 
     return;
   }
   if (!g_force_blocked_chol && ns + 1 <= CHOLP_MAX_N1) {
-    const int nb = (ns + 1 + CT - 1) / CT, nbc = (ns + CT - 1) / CT;
-    const size_t nlinv = (size_t)nb * CT * CT;
-    if (h->chol_linv.n < nlinv) h->chol_linv.alloc(nlinv, false);
-    for (int kt0 = 0; kt0 < nbc;) {
-      const int wt = cholp_panel_tiles(ns, kt0);
-      const size_t lds = cholp_lds_bytes(ns, kt0, wt);
-      raise_dynamic_lds((const void*)k_cholp_panel, h->device, lds);
-      hipLaunchKernelGGL(k_cholp_panel, dim3(1), dim3(CHOLP_THREADS), lds, h->stream, ns, kt0, wt, reg, buf, h->chol_linv.p,
-                         h->info.p, g_chol_prof);
-      const int k1 = kt0 + wt, m = nb - k1, nt = m * (m + 1) / 2;
-      if (k1 < nbc && nt > 0)
-        hipLaunchKernelGGL(k_cholp_trail, dim3((nt + 3) / 4), dim3(256), 0, h->stream, ns, kt0, wt, buf);
-      kt0 = k1;
-    }
+    launch_cholp_factor(h, ns, reg, buf);
     if (ns <= CHOLP_BACK_COLS)
       hipLaunchKernelGGL((k_cholp_back<1, 4>), dim3(1), dim3(CHOLP_BACK_THREADS), 0, h->stream, ns, (const double*)buf,
                          (const double*)h->chol_linv.p, ps);
@@ -888,6 +899,22 @@ static bool syrk3_enabled(const mcba_handle_s* h) {
   return h->use_mfma && (h->ntile >= 9 || (env != nullptr && env[0] == '1'));
 }
 
+// Schur step 2 over the K stacked rows of W' = [W | y] (ns + 1 columns): partial SYRK tiles into h->P
+void launch_schur_syrk(mcba_handle_s* h, int K) {
+  const Dims& d = h->d;
+  const int nt2 = h->ntile * (h->ntile + 1) / 2;
+  if (syrk3_enabled(h)) {
+    const int nt3 = (h->ntile + 2) / 3;
+    hipLaunchKernelGGL(k_schur_syrk3, dim3(h->ksplit, nt3 * (nt3 + 1) / 2), dim3(SYRK3_THREADS), 0, h->stream, K, d.ns + 1,
+                       h->ntile, h->ksplit, h->W.p, h->P.p);
+  } else if (h->use_mfma)
+    hipLaunchKernelGGL((k_schur_syrk<true>), dim3(h->ksplit, nt2), dim3(64), 0, h->stream, K, d.ns + 1, h->ntile,
+                       h->ksplit, h->W.p, h->P.p);
+  else
+    hipLaunchKernelGGL((k_schur_syrk<false>), dim3(h->ksplit, nt2), dim3(64), 0, h->stream, K, d.ns + 1, h->ntile,
+                       h->ksplit, h->W.p, h->P.p);
+}
+
 void launch_gn_solve(mcba_handle_s* h, double reg, bool root_rank, double* dots_out = nullptr,
                      double* tr_dev = nullptr, const TrRegPartials* trp = nullptr) {
   const Dims& d = h->d;
@@ -910,20 +937,10 @@ void launch_gn_solve(mcba_handle_s* h, double reg, bool root_rank, double* dots_
     else
       hipLaunchKernelGGL((k_schur_frame<6>), dim3(d.Fl), dim3(256), 0, h->stream, d, h->Hff.p, h->Hfs.p, h->dsc.p, h->gh.p, reg,
                          h->Lf.p, h->W.p, h->yf.p, tr_dev, z.vs, z.nvb, z.q, z.nq, z.first, z.Delta);
-    const int nt2 = h->ntile * (h->ntile + 1) / 2;
-    if (syrk3_enabled(h)) {
-      const int nt3 = (h->ntile + 2) / 3;
-      hipLaunchKernelGGL(k_schur_syrk3, dim3(h->ksplit, nt3 * (nt3 + 1) / 2), dim3(SYRK3_THREADS), 0, h->stream, K, d.ns + 1,
-                         h->ntile, h->ksplit, h->W.p, h->P.p);
-    } else if (h->use_mfma)
-      hipLaunchKernelGGL((k_schur_syrk<true>), dim3(h->ksplit, nt2), dim3(64), 0, h->stream, K, d.ns + 1, h->ntile,
-                         h->ksplit, h->W.p, h->P.p);
-    else
-      hipLaunchKernelGGL((k_schur_syrk<false>), dim3(h->ksplit, nt2), dim3(64), 0, h->stream, K, d.ns + 1, h->ntile,
-                         h->ksplit, h->W.p, h->P.p);
+    launch_schur_syrk(h, K);
   }
   const int total = d.ns * d.ns + d.ns;
-  hipLaunchKernelGGL(k_schur_reduce, dim3(std::min(2048, (4 * total + 255) / 256)), dim3(256), 0, h->stream, d, h->Hss.p,
+  hipLaunchKernelGGL(k_schur_reduce<>, dim3(std::min(2048, (4 * total + 255) / 256)), dim3(256), 0, h->stream, d, h->Hss.p,
                      h->dsc.p, h->gh.p, h->P.p, h->ntile, h->ksplit, K, root_rank ? 1.0 : 0.0, h->sbuf.p, tr_dev);
   call_allreduce(h, h->sbuf.p, (size_t)total, 0);
   launch_chol(h, d.ns, tr_dev ? 0.0 : reg, h->sbuf.p, h->ps.p);
@@ -942,6 +959,56 @@ void launch_gn_solve(mcba_handle_s* h, double reg, bool root_rank, double* dots_
     hipLaunchKernelGGL(k_shard_fold_dots, dim3(1), dim3(64), 0, h->stream, dots_out, gn_dot_blocks(d), d.shard_rank, W,
                        h->scal.p + h->sl.shard4);
     call_allreduce(h, h->scal.p + h->sl.shard4, (size_t)3 * W + 1, 0);
+  }
+}
+
+// name of parameter k of the INTERNAL vector (error messages of mcba_covariance)
+std::string param_name(const mcba_handle_s* h, int k) {
+  const Dims& d = h->d;
+  static const char* pose[6] = {"rx", "ry", "rz", "tx", "ty", "tz"};
+  auto in = [&](int off, int len) { return off >= 0 && k >= off && k < off + len; };
+  if (in(d.off_campose, 6 * d.C)) { const int q = k - d.off_campose; return "camera_poses[" + std::to_string(q / 6) + "]." + pose[q % 6]; }
+  if (in(d.off_boardpose, 6 * d.B)) { const int q = k - d.off_boardpose; return "board_poses[" + std::to_string(q / 6) + "]." + pose[q % 6]; }
+  if (in(d.off_motion, d.n_motion)) {
+    const int q = k - d.off_motion;
+    if (d.motion == MCBA_MOTION_HAND_EYE) return std::string(q < 6 ? "motion.world_wrt_base." : "motion.gripper_wrt_camera.") + pose[q % 6];
+    if (d.motion == MCBA_MOTION_ROLLING)
+      return std::string(q < 6 * d.F ? "motion.start[" : "motion.end[") + std::to_string((q % (6 * d.F)) / 6) + "]." + pose[q % 6];
+    return "motion.frames[" + std::to_string(q / 6) + "]." + pose[q % 6];
+  }
+  if (in(d.off_cameras, d.C * (5 + d.ND))) {
+    static const char* intr[5] = {"fx", "fy", "cx", "cy", "skew"};
+    const int q = k - d.off_cameras, c = q / (5 + d.ND), e = q % (5 + d.ND);
+    return "cameras[" + std::to_string(c) + "]." + (e < 5 ? std::string(intr[e]) : "dist[" + std::to_string(e - 5) + "]");
+  }
+  if (d.off_boards >= 0 && k >= d.off_boards) {
+    const int q = k - d.off_boards;
+    return "boards.points[" + std::to_string(q / 3) + "]." + "xyz"[q % 3];
+  }
+  return "?";
+}
+
+// internal index -> caller index (-1: a padding slot of a ragged camera block)
+std::vector<int32_t> int_to_ext(const mcba_handle_s* h) {
+  std::vector<int32_t> m((size_t)h->d.n, -1);
+  if (h->ext2int.empty())
+    for (int i = 0; i < h->d.n; ++i) m[i] = i;
+  else
+    for (int i = 0; i < h->n_ext; ++i) m[h->ext2int[i]] = i;
+  return m;
+}
+
+// caller indices of the shared (not eliminated) parameters, ascending; sh_int receives their shared-space index
+void cov_shared_layout(const mcba_handle_s* h, std::vector<int32_t>& sh_ext, std::vector<int32_t>* sh_int) {
+  const Dims& d = h->d;
+  const std::vector<int32_t> i2e = int_to_ext(h);
+  sh_ext.clear();
+  if (sh_int) sh_int->clear();
+  for (int s = 0; s < d.ns; ++s) {
+    const int e = i2e[d.shared_to_x(s)];
+    if (e < 0) continue;
+    sh_ext.push_back(e);
+    if (sh_int) sh_int->push_back(s);
   }
 }
 
@@ -1946,6 +2013,153 @@ int32_t mcba_dense_hessian(mcba_handle h, double* H) {
     for (int i = 0; i < ne; ++i)
       for (int j = 0; j < ne; ++j) H[(size_t)i * ne + j] = full[(size_t)h->ext2int[i] * d.n + h->ext2int[j]];
   }
+  API_END
+}
+
+
+int32_t mcba_covariance_layout(mcba_handle h, int32_t* n_shared, int32_t* df, int32_t* shared_index) {
+  API_BEGIN
+  REQUIRE(h, "null handle");
+  std::vector<int32_t> sh;
+  cov_shared_layout(h, sh, nullptr);
+  if (n_shared) *n_shared = (int32_t)sh.size();
+  if (df) *df = h->d.DF;
+  if (shared_index) std::copy(sh.begin(), sh.end(), shared_index);
+  API_END
+}
+
+int32_t mcba_covariance(mcba_handle h, const double* x, const uint8_t* hold, double sigma2, double* cov_shared,
+                        double* cov_frames, double* cov_frame_shared, double* std_out, double* sigma2_out, int64_t* dof_out) {
+  API_BEGIN
+  REQUIRE(h && x, "null argument");
+  g_fill_stream = h->stream;
+  const Dims& d = h->d;
+  REQUIRE(d.shard_world == 0 && d.f0 == 0 && d.Fl == d.F, "covariance: a frame-sharded handle is not supported (use a plain handle)");
+  REQUIRE(d.ns + 1 <= CHOLP_MAX_N1, "covariance: the reduced system has " + std::to_string(d.ns) + " shared parameters; at most " +
+                                        std::to_string(CHOLP_MAX_N1 - 1) + " are supported");
+  // the linear-loss normal equations at x: H = J^T J in block form, diag(H), cost = |r|^2 / 2
+  mcba_options lin{};
+  lin.loss = MCBA_LOSS_LINEAR;
+  lin.f_scale = 1.0;
+  set_loss(h, &lin);
+  upload_x(h, x, h->x.p);
+  launch_linearize(h, h->x.p);
+  launch_assemble(h);
+  const int n = d.n, ns = d.ns, DF = d.DF, Fl = d.Fl, K = DF * Fl;
+  HIP_OK(hipMemcpyAsync(h->h_gbuf, h->gbuf.p, (2 * (size_t)n + 2) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  sync(h);
+  const double* diag = h->h_gbuf + n;
+  const double cost = h->h_gbuf[2 * (size_t)n];
+  // D = diag(H)^-1/2 of the free, observed parameters; 0 for held (hold[i] != 0) and unobserved (diag(H) == 0) ones
+  const std::vector<int32_t> i2e = int_to_ext(h);
+  std::vector<double> D((size_t)n, 0.0);
+  std::vector<uint8_t> held((size_t)n, 0);
+  int64_t p_free = 0;
+  for (int k = 0; k < n; ++k) {
+    held[k] = (hold != nullptr && i2e[k] >= 0 && hold[i2e[k]] != 0) ? 1 : 0;
+    if (!held[k] && diag[k] > 0.0) {
+      D[k] = 1.0 / std::sqrt(diag[k]);
+      ++p_free;
+    }
+  }
+  const int64_t m = 2 * (int64_t)h->n_inliers, dof = m - p_free;
+  REQUIRE(dof > 0, "covariance: " + std::to_string(m) + " residuals do not determine " + std::to_string(p_free) +
+                       " free parameters (m <= p_free)");
+  const double s2 = sigma2 > 0.0 ? sigma2 : 2.0 * cost / (double)dof;
+  h->cov_d.alloc((size_t)n, false);
+  h->cov_zero.alloc((size_t)n, false);
+  HIP_OK(hipMemcpyAsync(h->cov_d.p, D.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemsetAsync(h->cov_zero.p, 0, (size_t)n * sizeof(double), h->stream));
+  // frame blocks and the reduced system in the scaled space, no damping, unit diagonal where D = 0
+  if (K > 0) {
+    if (DF == 12)
+      hipLaunchKernelGGL((k_schur_frame<12, true>), dim3(Fl), dim3(256), 0, h->stream, d, h->Hff.p, h->Hfs.p, h->cov_d.p, h->cov_zero.p,
+                         0.0, h->Lf.p, h->W.p, h->yf.p, (double*)nullptr, (const double*)nullptr, 0, (const double*)nullptr, 0, 0, 0.0);
+    else
+      hipLaunchKernelGGL((k_schur_frame<6, true>), dim3(Fl), dim3(256), 0, h->stream, d, h->Hff.p, h->Hfs.p, h->cov_d.p, h->cov_zero.p,
+                         0.0, h->Lf.p, h->W.p, h->yf.p, (double*)nullptr, (const double*)nullptr, 0, (const double*)nullptr, 0, 0, 0.0);
+    launch_schur_syrk(h, K);
+  }
+  const int total = ns * ns + ns;
+  hipLaunchKernelGGL(k_schur_reduce<true>, dim3(std::min(2048, (4 * total + 255) / 256)), dim3(256), 0, h->stream, d, h->Hss.p,
+                     h->cov_d.p, h->cov_zero.p, h->P.p, h->ntile, h->ksplit, K, 0.0, h->sbuf.p, (const double*)nullptr);
+  launch_cholp_factor(h, ns, 0.0, h->sbuf.p);
+  h->cov_bad.alloc(2, false);
+  const int32_t none[2] = {COV_PIVOT_NONE, COV_PIVOT_NONE};
+  HIP_OK(hipMemcpyAsync(h->cov_bad.p, none, sizeof(none), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_cov_pivots, dim3(std::max(1, std::min(1024, (K + ns + 255) / 256))), dim3(256), 0, h->stream, d,
+                     (const double*)h->Lf.p, (const double*)h->sbuf.p, h->cov_bad.p);
+  int32_t bad[2];
+  HIP_OK(hipMemcpyAsync(bad, h->cov_bad.p, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+  sync(h);
+  check_launch("covariance factors");
+  for (int q = 0; q < 2; ++q)   // (frame blocks are factored first: their report wins)
+    if (bad[q] != COV_PIVOT_NONE)
+      throw Error("covariance: rank deficient at x[" + std::to_string(i2e[bad[q]]) + "] (" + param_name(h, bad[q]) +
+                  "); hold more parameters");
+  // Sigma_ss = L^-T L^-1
+  const int nsp = (ns + CT - 1) / CT * CT, ntile_s = nsp / CT, nt2s = ntile_s * (ntile_s + 1) / 2;
+  constexpr int COV_KSPLIT = 8;
+  h->cov_x.alloc((size_t)ns * ns, false);
+  h->cov_p.alloc((size_t)COV_KSPLIT * nt2s * 256, false);
+  h->cov_sg.alloc((size_t)nsp * nsp, false);
+  h->cov_sout.alloc((size_t)ns * ns, false);
+  HIP_OK(hipMemsetAsync(h->cov_x.p, 0, (size_t)ns * ns * sizeof(double), h->stream));
+  const size_t lds_t = cov_trinv_lds_bytes(ns);
+  raise_dynamic_lds((const void*)k_cov_trinv, h->device, lds_t);
+  hipLaunchKernelGGL(k_cov_trinv, dim3(ntile_s), dim3(COV_TRINV_THREADS), lds_t, h->stream, ns, (const double*)h->sbuf.p,
+                     (const double*)h->chol_linv.p, h->cov_x.p);
+  hipLaunchKernelGGL((k_schur_syrk<true>), dim3(COV_KSPLIT, nt2s), dim3(64), 0, h->stream, ns, ns, ntile_s, COV_KSPLIT,
+                     (const double*)h->cov_x.p, h->cov_p.p);
+  hipLaunchKernelGGL(k_cov_fold, dim3(std::min(2048, (nsp * nsp + 255) / 256)), dim3(256), 0, h->stream, d, (const double*)h->cov_p.p,
+                     ntile_s, COV_KSPLIT, (const double*)h->cov_d.p, s2, nsp, h->cov_sg.p, h->cov_sout.p);
+  // per-frame marginal blocks (+ cross blocks)
+  const bool want_fs = cov_frame_shared != nullptr && K > 0;
+  if (K > 0) {
+    h->cov_ff.alloc((size_t)K * DF, false);
+    if (want_fs) h->cov_fs.alloc((size_t)K * ns, false);
+    const size_t lds_f = cov_frame_lds_bytes(nsp);
+    double* fs = want_fs ? h->cov_fs.p : nullptr;
+    if (DF == 12) {
+      raise_dynamic_lds((const void*)k_cov_frame<12>, h->device, lds_f);
+      hipLaunchKernelGGL((k_cov_frame<12>), dim3(Fl), dim3(COV_FRAME_THREADS), lds_f, h->stream, d, (const double*)h->Lf.p,
+                         (const double*)h->W.p, (const double*)h->cov_sg.p, nsp, (const double*)h->cov_d.p, s2, h->cov_ff.p, fs);
+    } else {
+      raise_dynamic_lds((const void*)k_cov_frame<6>, h->device, lds_f);
+      hipLaunchKernelGGL((k_cov_frame<6>), dim3(Fl), dim3(COV_FRAME_THREADS), lds_f, h->stream, d, (const double*)h->Lf.p,
+                         (const double*)h->W.p, (const double*)h->cov_sg.p, nsp, (const double*)h->cov_d.p, s2, h->cov_ff.p, fs);
+    }
+  }
+  check_launch("covariance kernels");
+  // downloads; rows / columns of the shared block in the caller's order
+  std::vector<double> sout((size_t)ns * ns), ff((size_t)K * DF), fsv(want_fs ? (size_t)K * ns : 0);
+  HIP_OK(hipMemcpyAsync(sout.data(), h->cov_sout.p, sout.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (K > 0) HIP_OK(hipMemcpyAsync(ff.data(), h->cov_ff.p, ff.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (want_fs) HIP_OK(hipMemcpyAsync(fsv.data(), h->cov_fs.p, fsv.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  sync(h);
+  std::vector<int32_t> sh_ext, sh_int;
+  cov_shared_layout(h, sh_ext, &sh_int);
+  const size_t nsh = sh_int.size();
+  if (cov_shared)
+    for (size_t a = 0; a < nsh; ++a)
+      for (size_t b = 0; b < nsh; ++b) cov_shared[a * nsh + b] = sout[(size_t)sh_int[a] * ns + sh_int[b]];
+  if (cov_frames && K > 0) std::copy(ff.begin(), ff.end(), cov_frames);
+  if (cov_frame_shared && K > 0)
+    for (size_t r = 0; r < (size_t)K; ++r)
+      for (size_t b = 0; b < nsh; ++b) cov_frame_shared[r * nsh + b] = fsv[r * ns + sh_int[b]];
+  if (std_out) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<double> var((size_t)n, 0.0);
+    for (int s = 0; s < ns; ++s) var[d.shared_to_x(s)] = sout[(size_t)s * ns + s];
+    for (int fl = 0; fl < Fl; ++fl)
+      for (int i = 0; i < DF; ++i) var[d.frame_to_x(d.f0 + fl, i)] = ff[((size_t)fl * DF + i) * DF + i];
+    for (int k = 0; k < n; ++k) {
+      if (i2e[k] < 0) continue;
+      std_out[i2e[k]] = held[k] ? 0.0 : (D[k] == 0.0 ? nan : std::sqrt(std::max(var[k], 0.0)));
+    }
+  }
+  if (sigma2_out) *sigma2_out = s2;
+  if (dof_out) *dof_out = dof;
   API_END
 }
 

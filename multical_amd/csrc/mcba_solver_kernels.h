@@ -1055,6 +1055,9 @@ __global__ __launch_bounds__(SYRK3_THREADS, 2) void k_schur_syrk3(int K, int nco
 //                rhs = [own shared gradient] - W^T y.   buf = [S (ns*ns) | rhs (ns)]: rhs is "row ns" of the matrix.
 // FOUR threads per element: thread q of a quad sums the splits q, q + 4, ... (four loads in flight each), the quad is
 // folded with two shuffles in a fixed order.  One thread per element walked its 32 splits as eight dependent round trips.
+// UNIT (the covariance route, mcba_covariance): a parameter with scale dsc = 0 (held or unobserved) gets a unit diagonal --
+// its row and column of D H D are already zero, so it leaves the rest of the system alone.
+template <bool UNIT = false>
 __global__ __launch_bounds__(256) void k_schur_reduce(Dims d, const double* __restrict__ Hss, const double* __restrict__ dsc,
                                                       const double* __restrict__ gh, const double* __restrict__ P, int ntile,
                                                       int ksplit, int K, double g_weight, double* __restrict__ buf,
@@ -1093,8 +1096,13 @@ __global__ __launch_bounds__(256) void k_schur_reduce(Dims d, const double* __re
     sum += __shfl_down(sum, 1, 4);
     if (q != 0 || !wanted) continue;
     // (the damping lives on the device, tr[TR_REG]; only the root rank adds it: the buffer is summed over the ranks next)
-    if (i < ns) buf[e] = dsc[d.shared_to_x(i)] * Hss[e] * dsc[d.shared_to_x(j)] - sum + ((tr != nullptr && i == j) ? g_weight * tr[TR_REG] : 0.0);
-    else buf[e] = g_weight * gh[d.shared_to_x(j)] - sum;
+    if (i < ns) {
+      double v = dsc[d.shared_to_x(i)] * Hss[e] * dsc[d.shared_to_x(j)] - sum + ((tr != nullptr && i == j) ? g_weight * tr[TR_REG] : 0.0);
+      if constexpr (UNIT) {
+        if (i == j && dsc[d.shared_to_x(i)] == 0.0) v = 1.0;
+      }
+      buf[e] = v;
+    } else buf[e] = g_weight * gh[d.shared_to_x(j)] - sum;
   }
 }
 
@@ -1874,7 +1882,8 @@ __global__ void k_cholb_back_update(int ns, int k0, double* __restrict__ A) {
 //     LDS): W[:, s], and y = W[:, ns].
 // L (strict lower part) with 1 / L_ii on the diagonal is kept for the back substitution (Lf [Fl][DF][DF]).
 // ---------------------------------------------------------------------------------------------------------------
-template <int DF>
+// UNIT (the covariance route): a frame parameter with scale dsc = 0 (held or unobserved) gets a unit diagonal in A_ff.
+template <int DF, bool UNIT = false>
 __global__ __launch_bounds__(256, 2) void k_schur_frame(Dims d, const double* __restrict__ Hff, const double* __restrict__ Hfs,
                                                     const double* __restrict__ dsc, const double* __restrict__ gh, double reg,
                                                     double* __restrict__ Lf, double* __restrict__ W, double* __restrict__ yf,
@@ -1899,6 +1908,9 @@ __global__ __launch_bounds__(256, 2) void k_schur_frame(Dims d, const double* __
     const int i = tid >> 4, j = tid & 15;   // 256 threads = the 16 x 16 tile
     double v = (i == j) ? 1.0 : 0.0;
     if (i < DF && j < DF) v = df_s[i] * hff[i * DF + j] * df_s[j] + (i == j ? reg_s : 0.0);
+    if constexpr (UNIT) {
+      if (i == j && i < DF && df_s[i] == 0.0) v = 1.0;
+    }
     Dt[i * CTL + j] = v;
   }
   __syncthreads();

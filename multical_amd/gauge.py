@@ -7,6 +7,7 @@ different points of that 12-dimensional null space, so raw parameter vectors are
 calibration to the gauge "first valid camera at the origin, first valid board at the origin" and `parameter_deltas` reports
 physical differences in that gauge: focal length (relative), principal point (px), distortion coefficients (absolute),
 rotation angle (degrees) and translation (in board units, metres for the example boards) of camera, frame and board poses.
+`default_hold` is the same gauge as a mask over `Calibration.param_vec`: the parameters a covariance holds fixed.
 """
 import numpy as np
 
@@ -67,3 +68,30 @@ def parameter_deltas(a, b):
   d = d._extend(frame_deg=fdeg, frame_t=ft)
   d = d._extend(**dict(zip(("board_deg", "board_t"), _pose_delta(ca.boards, cb.boards, ca.board_valid & cb.board_valid))))
   return d
+
+
+def default_hold(calib):
+  """Held-parameter mask (bool, over calib.param_vec) of the gauge `canonical` uses: the 6 pose parameters of the first valid
+  camera (if camera_poses are optimised) and of the first valid board (if board_poses are optimised).  For static and
+  rolling-shutter motion this removes exactly the 12-dimensional null space; for hand-eye motion world_wrt_base and
+  gripper_wrt_camera absorb the same two freedoms, so the same hold applies.  With the `boards` block optimised (board points
+  adjusted) every board has 6 more rigid-body freedoms and there is a global scale: no default exists, and ValueError asks
+  for an explicit hold."""
+  from . import parameters
+  opt = calib.optimize
+  if opt["boards"] is True:
+    raise ValueError("covariance: with the boards block optimised the default hold does not fix the gauge (each board's "
+                     "points have 6 rigid-body freedoms and the rig a global scale); pass an explicit hold mask")
+  sizes = [(k, parameters.count(calib.params[k])) for k in ("camera_poses", "board_poses", "motion", "cameras", "boards")
+           if opt[k] is True]
+  hold = np.zeros(sum(n for _, n in sizes), dtype=bool)
+  pos = 0
+  for k, n in sizes:
+    if k == "camera_poses":
+      c0 = _first_valid(calib.camera_poses.valid)
+      hold[pos + 6 * c0:pos + 6 * c0 + 6] = True
+    elif k == "board_poses":
+      b0 = _first_valid(calib.board_poses.valid)
+      hold[pos + 6 * b0:pos + 6 * b0 + 6] = True
+    pos += n
+  return hold
