@@ -128,6 +128,10 @@ CONFIGS = {
   # tables (tables.py:44-56; the reference's default limit, config/arguments.py:50)
   "cfg5": dict(cameras=6, frames=400, boards=["charuco_10x10"] * 5, motion="static", model="fisheye",
                optimize_cameras=True, layout="ring", seed=5, pose_error_limit=1.0, pose_noise=(2e-4, 1e-4)),
+  # cfg5's rig driven by the hand-eye motion model (HandEyeCalibration, optimization/hand_eye.py): no per-frame parameters --
+  # every observation lands in the 12 hand-eye columns plus its board pose; cameras and camera poses are held fixed
+  "cfg5_handeye": dict(cameras=6, frames=400, boards=["charuco_10x10"] * 5, motion="hand_eye", model="fisheye",
+                       optimize_cameras=False, layout="ring", seed=5, pose_error_limit=1.0, pose_noise=(2e-4, 1e-4)),
   # small variants used by unit tests / smoke (same generators, fewer frames)
   "tiny": dict(cameras=2, frames=6, boards=["charuco_10x10"], motion="static", model="standard",
                optimize_cameras=True, layout="stereo", seed=11),

@@ -115,6 +115,7 @@ FULL_CASES = {
   "cfg3_full": "cfg3",     # 8 x 500 x 2 rolling shutter: the rig bench.py measures
   "cfg4_full": "cfg4",     # 16 x 1000 x 5
   "cfg5_full": "cfg5",     # 6 x 400 x 5 fisheye hand-eye
+  "cfg5_handeye_full": "cfg5_handeye",   # the same rig under the HandEye motion model (no per-frame block)
 }
 N_PERT = int(os.environ.get("MCBA_GOLDEN_NPERT", "10"))   # perturbed re-runs per reference call (oracle/make_pert.py widened the older
                                                           # fixtures to the same 10; the 160-pair rig keeps 3: 44 reference solves of

@@ -123,7 +123,7 @@ def endpoint_spread(g):
   return float(np.abs(g["ba_pert_rms"] - g["ba_rms"]).max()) if "ba_pert_rms" in g else 0.0
 
 
-@pytest.mark.parametrize("cfg", ["cfg3", "cfg5", "cfg4"])
+@pytest.mark.parametrize("cfg", ["cfg3", "cfg5", "cfg4", "cfg5_handeye"])
 def test_lsmr_mode_reproduces_the_reference_end_point_at_full_size(cfg, record_property):
   """BASELINE configs[2] (8 x 500 x 2 rolling shutter: the rig bench.py measures), configs[4] (6 x 400 x 5 fisheye) and configs[3]
   (16 x 1000 x 5) AT THEIR STATED SIZE: the unmodified reference's `Calibration.bundle_adjust()` end point (final RMS, nfev,
@@ -151,7 +151,7 @@ def test_lsmr_mode_reproduces_the_reference_end_point_at_full_size(cfg, record_p
   assert rms_native <= float(g["ba_rms"]) + max(1e-6, spread)
 
 
-@pytest.mark.parametrize("cfg", ["cfg3", "cfg5", "cfg4"])
+@pytest.mark.parametrize("cfg", ["cfg3", "cfg5", "cfg4", "cfg5_handeye"])
 def test_workspace_calibrate_at_full_size_against_the_reference(cfg):
   """Workspace.calibrate's outlier loop (workspace.py:228-247 -> calibration.py:254-268) at the stated size under solver="lsmr":
   the reference's inlier mask after three rounds, bit for bit, and its inlier RMS."""
@@ -271,7 +271,7 @@ def test_workspace_calibrate_under_the_default_solver(name):
   assert abs(rms_inl - float(g["ao_rms_inliers"])) <= max(1e-6, 3 * spread), (rms_inl, float(g["ao_rms_inliers"]), spread)
 
 
-@pytest.mark.parametrize("cfg", ["cfg5", "cfg3"])
+@pytest.mark.parametrize("cfg", ["cfg5", "cfg3", "cfg5_handeye"])
 def test_workspace_calibrate_with_a_robust_loss_at_full_size(cfg):
   """Workspace.calibrate(loss='soft_l1', auto_scale=2.0) (workspace.py:239-244: the soft margin re-derived from the error quantile in
   every round) at the stated size under the default solver, against the unmodified reference's run of the same loop."""
@@ -299,10 +299,15 @@ def test_workspace_calibrate_with_a_robust_loss_at_full_size(cfg):
 # The device's LSMR at the level of ONE lsmr() call (scipy/sparse/linalg/_isolve/lsmr.py:300-420, called at _lsq/trf.py:481)
 # ---------------------------------------------------------------------------------------------------------------------------------
 CALL_CASES = ["cfg1", "tiny_handeye", "tiny_fixintr", "tiny_rolling", "tiny_fisheye", "tiny_boards", "cfg2", "cfg3_40", "cfg4_40", "cfg5_40",
-              "manypairs"]
+              "manypairs", "cfg5_handeye"]
+# the iteration forms of the LSMR call (Handle.set_lsmr_fused): -1 = automatic (3 on static / hand-eye rigs, 2 with rolling shutter or
+# boards=True), 3 = two launches with the per-observation state cached, 2 = two launches, 1 = three, 0 = six
+LSMR_FORMS = (-1, 3, 2, 1, 0)
 
 
 def _load_any(name):
+  if name == "cfg5_handeye":                # (full size: the rig is regenerated from its seed, the fixture holds the end points)
+    return load_endpoint(name)
   if name in ("cfg2", "cfg3_40", "cfg4_40", "cfg5_40", "manypairs"):
     g = dict(np.load(os.path.join(GOLDEN, f"{name}.npz"), allow_pickle=False))
     return g, synthetic.make_rig(str(g["config"]))
@@ -338,7 +343,7 @@ def test_device_lsmr_first_steps_equal_scipys(name):
     J, f, d, damp = _first_iterate(h, x0)
     for k in (1, 3, 5) + ((10,) if h.n_params >= 100 else ()):
       ref = lsmr(scaled_operator(J, d), f, damp=damp, maxiter=k)
-      for form in (2, 1, 0):
+      for form in LSMR_FORMS:
         h.set_lsmr_fused(form)
         _, scale, _ = h.lsmr_solve(x0, damp, maxiter=1)
         assert np.abs(scale / d - 1).max() <= 1e-11           # (the device's own first-iterate scaling: sqrt of diag(J^T J) from the block records)
@@ -355,14 +360,17 @@ def test_device_lsmr_call_matches_scipy(name, record_property):
   few iterations of scipy's count, and its solution solves the damped problem to the SAME level -- measured with the matrix itself
   (host CSR arithmetic), not with either side's recurrence estimates: the true test2 = |A^T r - damp^2 x| / (|A|_F |r|) of the device's
   solution is within a factor 2 of that of scipy's, the damped objectives agree to what the stopping rule leaves open.  The recurrence scalars themselves are
-  compared where that is meaningful (test_device_lsmr_first_steps_equal_scipys)."""
+  compared where that is meaningful (test_device_lsmr_first_steps_equal_scipys).  Every iteration form of the call is held to this."""
   from scipy.sparse.linalg import lsmr
   from lsmr_emulation import scaled_operator
   g, rig = _load_any(name)
+  calls = {}
   with Handle(mirror(rig)) as h:
     x0 = g["x0"]
     J, f, d, damp = _first_iterate(h, x0)
-    gn, scale, info = h.lsmr_solve(x0, damp, scale=d)
+    for form in LSMR_FORMS:
+      h.set_lsmr_fused(form)
+      calls[form] = h.lsmr_solve(x0, damp, scale=d)
   ref = lsmr(scaled_operator(J, d), f, damp=damp)
   Jh = J @ __import__("scipy.sparse", fromlist=["diags"]).diags(d)
   normA_F = np.sqrt(Jh.power(2).sum() + damp ** 2 * J.shape[1])
@@ -371,22 +379,23 @@ def test_device_lsmr_call_matches_scipy(name, record_property):
     r = f - Jh @ p
     rbar = np.sqrt(r @ r + damp ** 2 * (p @ p))
     return np.linalg.norm(Jh.T @ r - damp ** 2 * p) / (normA_F * rbar), 0.5 * rbar ** 2
-  t2_dev, obj_dev = true_tests(gn)
   t2_ref, obj_ref = true_tests(ref[0])
-  record_property("itn_device_scipy", (info["itn"], int(ref[2])))
-  record_property("true_test2_device_scipy", (float(t2_dev), float(t2_ref)))
-  print(f"{name}: istop {info['istop']} / {ref[1]}, itn {info['itn']} / {ref[2]}, true test2 {t2_dev:.2e} / {t2_ref:.2e}, "
-        f"objective rel diff {abs(obj_dev - obj_ref) / obj_ref:.1e}, |x_dev - x_scipy| / |x| {np.linalg.norm(gn - ref[0]) / np.linalg.norm(ref[0]):.1e}")
-  assert info["istop"] == int(ref[1]), (info, ref[1:3])
-  assert abs(info["itn"] - int(ref[2])) <= max(3, 0.02 * int(ref[2])), (info["itn"], int(ref[2]))
-  # (atol = 1e-6: below a tenth of it both solutions are converged to rounding and the ratio means nothing -- tiny_handeye: 4e-9 / 8e-9)
-  assert t2_dev <= 2.0 * t2_ref + 1e-7 and t2_ref <= 2.0 * t2_dev + 1e-7, (t2_dev, t2_ref)
-  # (two approximate minimisers stopped by the same rule: their objectives differ by what atol = 1e-6 leaves open -- 1e-8 ... 1e-6
-  #  relative on these fixtures, more where the call runs into maxiter, istop 7)
-  assert abs(obj_dev - obj_ref) <= (1e-5 if info["istop"] in (1, 2) else 1e-3) * obj_ref
+  for form, (gn, scale, info) in calls.items():
+    t2_dev, obj_dev = true_tests(gn)
+    record_property(f"form{form}_itn_device_scipy", (info["itn"], int(ref[2])))
+    record_property(f"form{form}_true_test2_device_scipy", (float(t2_dev), float(t2_ref)))
+    print(f"{name} form {form}: istop {info['istop']} / {ref[1]}, itn {info['itn']} / {ref[2]}, true test2 {t2_dev:.2e} / {t2_ref:.2e}, "
+          f"objective rel diff {abs(obj_dev - obj_ref) / obj_ref:.1e}, |x_dev - x_scipy| / |x| {np.linalg.norm(gn - ref[0]) / np.linalg.norm(ref[0]):.1e}")
+    assert info["istop"] == int(ref[1]), (form, info, ref[1:3])
+    assert abs(info["itn"] - int(ref[2])) <= max(3, 0.02 * int(ref[2])), (form, info["itn"], int(ref[2]))
+    # (atol = 1e-6: below a tenth of it both solutions are converged to rounding and the ratio means nothing -- tiny_handeye: 4e-9 / 8e-9)
+    assert t2_dev <= 2.0 * t2_ref + 1e-7 and t2_ref <= 2.0 * t2_dev + 1e-7, (form, t2_dev, t2_ref)
+    # (two approximate minimisers stopped by the same rule: their objectives differ by what atol = 1e-6 leaves open -- 1e-8 ... 1e-6
+    #  relative on these fixtures, more where the call runs into maxiter, istop 7)
+    assert abs(obj_dev - obj_ref) <= (1e-5 if info["istop"] in (1, 2) else 1e-3) * obj_ref, form
 
 
-@pytest.mark.parametrize("name", ["cfg1", "tiny_handeye", "tiny_fixintr", "cfg2", "cfg3_40", "cfg4_40", "cfg5_40", "manypairs"])
+@pytest.mark.parametrize("name", ["cfg1", "tiny_handeye", "tiny_fixintr", "cfg2", "cfg3_40", "cfg4_40", "cfg5_40", "manypairs", "cfg5_handeye"])
 def test_lsmr_call_sequence_of_a_solve(name):
   """the per-trust-region-iteration (istop, itn) sequence of the default solver (mcba_debug_lsmr_trace) against scipy's own TRF + LSMR on
   the device's residuals / Jacobian (tests/lsmr_emulation.trf_lsmr): the same stopping reasons in the same order -- including the
@@ -409,7 +418,7 @@ def test_lsmr_call_sequence_of_a_solve(name):
   assert sum(c["itn"] for c in trace) == total and res.nfev == int(g["ba_nfev"])
 
 
-@pytest.mark.parametrize("cfg", ["cfg5", "cfg3", "cfg4"])
+@pytest.mark.parametrize("cfg", ["cfg5", "cfg3", "cfg4", "cfg5_handeye"])
 def test_converged_optimum_at_full_size(cfg, record_property):
   """SURVEY 7, protocol C at the STATED sizes of BASELINE configs[2] / [3] / [4]: the converged optimum of the REFERENCE's own residual
   function (tests/golden/cfg*_endpoint.npz: ba_tight_*, oracle/make_endpoint.py tight -- Levenberg-Marquardt on the reference's
@@ -440,14 +449,14 @@ def _exact_products():
   return json.load(open(path)) if os.path.exists(path) else {}
 
 
-@pytest.mark.parametrize("name", ["cfg2", "cfg3_40", "cfg4_40", "cfg5_40", "manypairs", "cfg5", "cfg3"])
+@pytest.mark.parametrize("name", ["cfg2", "cfg3_40", "cfg4_40", "cfg5_40", "manypairs", "cfg5", "cfg3", "cfg4"])
 def test_default_solver_lands_on_scipys_exact_product_end_point(name, record_property):
   """WHY the default solver ends a few 1e-6 px BELOW the reference's single run on every BASELINE-size rig (round-5 review): scipy's own
   algorithm on the reference's residual function (tests/golden/exact_products.json, oracle/make_exact_products.py) ends in two
   clusters -- with scipy.sparse's double products anywhere within ~1e-6 px of the reference's run (that IS the reference's
   arithmetic; its run-to-run spread), and with the same products accumulated in 80-bit precision 1e-7 ... 2.5e-6 px lower, tightly.
   The device's products (per-lane partial sums + tree reductions: a few ulp) are of the second kind: the default solver lands on the
-  exact-product end point of scipy's algorithm within 1e-6 px on the 40-frame rigs and 6 x 400 x 5, in all three iteration forms (at
+  exact-product end point of scipy's algorithm within 1e-6 px on the 40-frame rigs and 6 x 400 x 5, in every iteration form (at
   8 x 500 x 2 and 16 x 1000 x 5 scipy's own variants spread over 1e-6 px among themselves: the reference's measured spread is the tolerance)."""
   xp = _exact_products().get(name)
   if xp is None or "longdouble_mean_rms" not in xp:
@@ -460,7 +469,7 @@ def test_default_solver_lands_on_scipys_exact_product_end_point(name, record_pro
   runs = [r["rms"] for r in xp["runs"]]
   tol = 1e-6 if (max(runs) - min(runs) <= 3e-6 and name not in ("cfg3", "cfg4")) else max(1e-6, endpoint_spread(g))
   with Handle(mirror(rig)) as h:
-    for form in (2, 1, 0):
+    for form in LSMR_FORMS:
       h.set_lsmr_fused(form)
       res = h.solve(g["x0"], tr_solver="lsmr")
       e, v = h.reprojection_error(res.x)

@@ -370,10 +370,10 @@ def test_full_size_properties_cfg2():
     assert np.abs(g2 / si).max() < 1e-3 * np.sqrt(2 * res.cost)
 
 
-@pytest.mark.parametrize("name", ["cfg3", "cfg4", "cfg5"])
+@pytest.mark.parametrize("name", ["cfg3", "cfg4", "cfg5", "cfg5_handeye"])
 def test_full_size_properties(name):
   """BASELINE configs[2..4] AT THEIR STATED SIZE (rolling shutter 8x500x2 = the rig bench.py measures, 16x1000x5,
-  fisheye hand-eye 6x400x5), pinned to the real reference: tests/golden/<name>_full.npz holds checksums, a strided
+  fisheye 6x400x5) and the 6x400x5 rig under the hand-eye motion model (no per-frame block), pinned to the real reference: tests/golden/<name>_full.npz holds checksums, a strided
   sample and the error statistics of the reference's `evaluate` / `reprojection_error` at x0 and at a perturbed point,
   and a central-difference directional derivative of its cost (oracle/make_golden.py: run_full_case).  The WHOLE
   residual vector and error table are additionally compared with the oracle (which reproduces the reference bit for
@@ -646,6 +646,14 @@ for name in ["tiny", "tiny_rolling", "tiny_handeye", "tiny_fisheye", "tiny_edge"
     res = h.solve(g["x0"])
   out[name] = dict(cost=cost, grad=grad.tolist(), hsum=float(np.abs(H).sum()), H=H.ravel()[::7].tolist(), nfev=res.nfev,
                    final=res.cost)
+from multical_amd import synthetic   # the hand-eye rig at full size (no per-frame block: chunk sums only, DF == 0 in k_shared_final)
+c = mirror(synthetic.make_rig("cfg5_handeye"))
+with Handle(c) as h:
+  cost, grad, diag = h.normal_equations(c.param_vec)
+  H = h.dense_hessian()
+  res = h.solve(c.param_vec)
+out["cfg5_handeye"] = dict(cost=cost, grad=grad.tolist(), hsum=float(np.abs(H).sum()), H=H.ravel()[::7].tolist(), nfev=res.nfev,
+                           final=res.cost)
 print("RESULT" + json.dumps(out))
 '''
   root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -74,10 +74,11 @@ def check_full_residuals(g, tag, r, tol):
   assert abs(np.dot(r, np.cos(np.arange(r.size) * 0.001)) - float(g[f"r{tag}_wsum"])) <= tol * r.size
 
 
-@pytest.mark.parametrize("name", ["cfg3", "cfg4", "cfg5"])
+@pytest.mark.parametrize("name", ["cfg3", "cfg4", "cfg5", "cfg5_handeye"])
 def test_oracle_matches_reference_at_full_size(name):
-  """BASELINE configs[2..4] at their stated size (8x500x2 rolling, 16x1000x5, 6x400x5 fisheye hand-eye): the oracle's
-  whole residual vector and error statistics against the real reference's checksums, at x0 and at a perturbed point."""
+  """BASELINE configs[2..4] at their stated size (8x500x2 rolling, 16x1000x5, 6x400x5 fisheye) and the 6x400x5 rig under the
+  hand-eye motion model: the oracle's whole residual vector and error statistics against the real reference's checksums, at x0
+  and at a perturbed point."""
   g, rig = full_golden(name)
   oc = oracle(rig)
   assert np.array_equal(oc.param_vec, g["x0"])
