@@ -1198,6 +1198,11 @@ int32_t mcba_create(const mcba_problem* p, void* hip_stream, mcba_handle* out) {
   const double tc1 = now_seconds();
   h->d = hp.d;
   Dims& d = h->d;
+  // MCBA_STORE_THROUGH: on / off.  0 = plain stores to the hand-off buffers (A/B runs, tests), anything else = the default
+  // (write-through at every adopted site).  MCBA_STORE_THROUGH_SITES = mask of STORE_THROUGH_* bits: one site alone, for the
+  // site-by-site record in profiles/store_policy.txt; it narrows what "on" means and is ignored with the switch off.
+  if (const char* e = dbg_switch("MCBA_STORE_THROUGH")) if (e[0] == '0') d.store_through = 0;
+  if (const char* e = dbg_switch("MCBA_STORE_THROUGH_SITES")) d.store_through &= atoi(e);
   h->ext2int = hp.ext2int;
   h->n_ext = hp.n_ext;
   if (!hp.cam_kmask.empty()) {

@@ -17,6 +17,8 @@ namespace mcba {
 // 2048 -> 74.9, 3072 -> 72.4, 4096 -> 65.7, 4401 (one view each) -> 67.6, exactly 3 views each (1467, ascending) -> 112 us.
 constexpr int LIN_GRID_MAX = 4096;
 constexpr int MOTION_STATIC = 0, MOTION_ROLLING = 1, MOTION_HAND_EYE = 2;
+// Dims::store_through: the records of k_linearize; the frame blocks and chunk sums of k_assemble
+constexpr int STORE_THROUGH_RECORDS = 1, STORE_THROUGH_ASSEMBLY = 2;
 
 // Problem shape + index maps, passed BY VALUE to every kernel (fits the kernarg segment).
 struct Dims {
@@ -57,6 +59,9 @@ struct Dims {
   // only -- nothing of length n ever crosses the ranks; sums over all parameters are formed as all-reduced per-rank partial
   // sums in which every entry is counted exactly once (entry_weight).
   int shard_rank, shard_world;
+  // Hand-off buffers (read by the NEXT kernel only) are stored write-through: store_through() below.  Wave-uniform
+  // STORE_THROUGH_* bits, so one build carries both policies (debug switch MCBA_STORE_THROUGH=0: plain stores).
+  int store_through;
 
   // global x index of a shared-parameter index (x order with the eliminated motion block removed)
   MCBA_HD int shared_to_x(int s) const {
@@ -130,5 +135,28 @@ struct LsmrCompact {
                            //             observation: the division leaves the head of every evaluation's dependency chain); else null
   const int4* desc;        // [active views] {v, first, count, 0}
 };
+
+#if defined(__HIPCC__)
+// Write-through stores for hand-off buffers.  A plain store leaves its line dirty in the XCD's L2 and the end of the kernel
+// writes all of them back before a dependent launch starts; a store with the agent-scope (sc1) policy goes through the L2
+// while the kernel still runs.  Cache policy only: the bytes are the same.
+//   8 bytes:  a relaxed agent-scope atomic store = global_store_dwordx2 ... sc1 (keeps the pointer's provenance)
+//  16 bytes:  one buffer_store_dwordx4 ... sc1 through a resource over [base, base + bytes) -- base and bytes wave-uniform,
+//             offset per lane.  (A double2 as two 8-byte halves: the records of k_linearize gained 1.1 instead of 1.45 us.)
+// The atomic form is ordered against every other access in hipcc's alias analysis: in a kernel whose wave-uniform table reads
+// are scalar loads only because nothing can clobber them (k_lsmr_fused2) its mere presence turns them into vector loads.
+__device__ __forceinline__ void store_through(double* p, double v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+typedef unsigned int store_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t store_through_resource(void* base, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000);   // raw buffer, 32-bit data format
+}
+__device__ __forceinline__ void store_through16(__amdgpu_buffer_rsrc_t r, int byte_offset, double2 v) {
+  store_u32x4 w;
+  __builtin_memcpy(&w, &v, 16);
+  __builtin_amdgcn_raw_buffer_store_b128(w, r, byte_offset, 0, 16);             // aux 16 = sc1
+}
+#endif
 
 }  // namespace mcba

@@ -982,6 +982,9 @@ __global__ __launch_bounds__(64) MCBA_F2_OCCUPANCY void k_lsmr_fused2(Dims d, Ta
         for (int k = 0; k < KI; ++k) sums[DE + k] += cv[0] * ps.Kc[k] + cv[1] * ps.Kc[KIA + k];
       }
     }
+    // (plain store on purpose: uhat is read back by the SAME workgroup slot in the next iteration and stays in its XCD's L2;
+    //  store_through here measured 30.4 against 29.2 us with the switch off -- and 24.1 us without the store in the kernel at all:
+    //  the table reads left the scalar unit, profiles/store_policy.txt)
     reinterpret_cast<double2*>(u)[pair] = o;
     acc += o.x * o.x + o.y * o.y;
     if (bpart != nullptr) {
@@ -2148,8 +2151,15 @@ void k_linearize(Dims d, Tables t, double* __restrict__ rec,
     lds_fence();
     const double2* mp2 = reinterpret_cast<const double2*>(Mp);
     double2* out2 = reinterpret_cast<double2*>(out);
-    for (int e = el; e < RECP / 2; e += 64) out2[e] = mp2[e];
+    if (d.store_through & STORE_THROUGH_RECORDS) {   // (read by k_assemble only; the resource spans this view's record)
+      const __amdgpu_buffer_rsrc_t rr = store_through_resource(out, RECP * 8);
+      for (int e = el; e < RECP / 2; e += 64) store_through16(rr, 16 * e, mp2[e]);
+    } else {
+      for (int e = el; e < RECP / 2; e += 64) out2[e] = mp2[e];
+    }
   } else {
+    // (MFMA = false, the validation build with plain FMAs: this epilogue keeps plain stores whatever Dims::store_through says --
+    //  scattered 8-byte stores by tri_index, off the measured path)
     // epilogue.  lane j < N1 owns column j of the local system:
     //   y[a] = (S That)[a][j]  for the DE base rows  (That column j in registers, S rows are LDS broadcasts)
     //   M[i][j] = sum_a That[a][i] y[a]  (i < NPC, i <= j),   M[i][j] = S[DE + i - NPC][.]-row entries otherwise

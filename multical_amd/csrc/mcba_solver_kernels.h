@@ -335,7 +335,8 @@ __device__ __forceinline__ void assemble_frame_block(const Dims& d, const Tables
         const int kind = q[u].w & 255;
         double* dst = kind == FT_HFS ? hfs + q[u].z : (kind == FT_HFF ? hff + q[u].z : g + d.frame_to_x(f, q[u].z));
         if (s0 > 0) sum += *dst;
-        *dst = sum;
+        if (d.store_through & STORE_THROUGH_ASSEMBLY) store_through(dst, sum); else *dst = sum;   // (read by the Schur kernels only)
+        // (diag: 8 bytes per frame parameter, 24 KB in all -- plain, like the H_fs clear above and the empty-chunk zeroes below)
         if ((q[u].w >> 8) != 0) diag[d.frame_to_x(f, (q[u].w >> 8) - 1)] = sum;
       }
     }
@@ -413,8 +414,13 @@ __device__ __forceinline__ void shared_partial_block(const Dims& d, const Tables
           s1 += a1[u];
         }
       }
-      out[e0] = s0;
-      if (h1) out[e1] = s1;
+      if (d.store_through & STORE_THROUGH_ASSEMBLY) {   // (read by k_shared_final only)
+        store_through(out + e0, s0);
+        if (h1) store_through(out + e1, s1);
+      } else {
+        out[e0] = s0;
+        if (h1) out[e1] = s1;
+      }
     }
   }
 }
