@@ -316,6 +316,38 @@ int32_t mcba_covariance_layout(mcba_handle h, int32_t* n_shared, int32_t* df, in
 int32_t mcba_covariance(mcba_handle h, const double* x, const uint8_t* hold, double sigma2, double* cov_shared,
                         double* cov_frames, double* cov_frame_shared, double* std_out, double* sigma2_out, int64_t* dof_out);
 
+/* --- per-observation prediction covariance, leverage and studentised errors ------------------- */
+/* The covariance of the PREDICTED point of every table slot under the covariance above:  C_i = J_i Sigma J_i^T  (2 x 2).
+ * J, Sigma = sigma2 (J^T J)^-1, hold, "unobserved", sigma2, dof and the rank-deficiency rule are exactly mcba_covariance's
+ * (linear loss, current inliers, Jacobi-scaled factorisation, pivot < 1e-10 -> error that names the parameter, m <= p_free
+ * -> error).  Not part of the reference.
+ *   - slots: every slot (c, f, b, p) of the mask mcba_reprojection_error returns as `valid`, inlier or not.  J_i is the 2 x n
+ *     row pair of the model at the slot -- the row pair mcba_jacobian produces where the slot is an inlier; rolling shutter:
+ *     scan time from the OBSERVED row, as in mcba_project.  Held parameters contribute nothing.  If J_i has a non-zero entry
+ *     on a parameter that is unobserved and not held (a valid point in a frame without inliers: the prediction is not
+ *     constrained), C_i is NaN.  Invalid slots: 0.
+ *   - leverage: H_ii = C_i / sigma2 for an inlier; the covariance of its residual is sigma2 (I - H_ii), the covariance of
+ *     the prediction error of a valid slot that is not an inlier is sigma2 I + C_i.
+ *   - studentised error  d_i = sqrt(r_i^T Omega_i^-1 r_i),  r_i = projected - observed,  Omega_i = sigma2 I - C_i (inlier)
+ *     or sigma2 I + C_i (valid, not an inlier); under the model d_i^2 is chi-square with 2 degrees of freedom.  An inlier
+ *     whose H_ii has its larger eigenvalue >= 1 - 1e-9 is fitted exactly: d_i = +inf.  NaN where C_i is NaN, 0 at invalid slots.
+ *   - larger eigenvalue of a symmetric 2 x 2 (uu uv; uv vv), each operation rounded once:
+ *         (0.5 (uu + vv)) + sqrt((0.5 (uu - vv))^2 + uv^2)
+ *   - outputs (any may be NULL), per-slot arrays in the reference's [C,F,B,P] order:
+ *       pred_cov     [C,F,B,P,3]  (uu, uv, vv) of C_i
+ *       student      [C,F,B,P]    d_i
+ *       cam_max_std  [C]          max over the camera's valid slots of sqrt(max(larger eigenvalue of C_i, 0)); NaN slots are skipped
+ *       *trace_out                sum over the inliers of tr(H_ii), reduced on the device in a fixed order (bit-repeatable);
+ *                                 mathematically p_free = m - dof
+ *   - not supported (refused with a message): a frame-sharded handle; the `boards` block optimised (B P 3 board-point
+ *     parameters would join the shared system); reduced systems of more than 1023 shared parameters.
+ * Nothing of Sigma leaves the device: the covariance chain runs once, then one pass over all table slots forms C_i = sigma2 z z^T,
+ * z = M^-1 D J_i^T, from the block Cholesky factor M of the scaled system (csrc/mcba_obscov_kernels.h; a sum of squares: J_i Sigma
+ * J_i^T itself cancels by 1e4 .. 1e7).                                                                                */
+int32_t mcba_observation_covariance(mcba_handle h, const double* x, const uint8_t* hold, double sigma2,
+                                    double* pred_cov, double* student, double* cam_max_std,
+                                    double* sigma2_out, int64_t* dof_out, double* trace_out);
+
 /* --- initialisation tables (the producer of the hot path's inputs) ---------------------------- */
 /* matrix.align_transforms_robust (transform/matrix.py:140-153) for a batch of problems: problem p owns the pose pairs
  * [offsets[p], offsets[p+1]) of A and B (row-major 4x4 "points-transforming" matrices), `mask` (or NULL = all) selects

@@ -100,6 +100,10 @@ SYMBOLS = [
   ("mcba_covariance_layout", C.c_int32, [H, c_int32_p, c_int32_p, c_int32_p]),
   ("mcba_covariance", C.c_int32, [H, c_double_p, c_uint8_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p,
                                   c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_observation_covariance", C.c_int32, [H, c_double_p, c_uint8_p, C.c_double, c_double_p, c_double_p, c_double_p,
+                                              c_double_p, C.POINTER(C.c_int64), c_double_p]),
+  ("mcba_debug_observation_covariance_ms", C.c_int32, [H, c_double_p]),
+  ("mcba_debug_set_observation_covariance_route", C.c_int32, [H, C.c_int32]),
   ("mcba_solve", C.c_int32, [H, c_double_p, C.POINTER(Options), C.POINTER(Result)]),
   ("mcba_time_linearize", C.c_int32, [H, c_double_p, C.POINTER(Options), C.c_int32, c_double_p]),
   ("mcba_time_residuals", C.c_int32, [H, c_double_p, C.c_int32, c_double_p]),

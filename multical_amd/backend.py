@@ -350,6 +350,43 @@ class Handle(object):
       out = out._extend(frame_shared=fs)
     return out
 
+  def observation_covariance(self, x, hold=None, sigma2=None, cov=True, student=True):
+    """Covariance of the predicted point of every valid table slot, C_i = J_i Sigma J_i^T with Sigma of `covariance` (same hold,
+    sigma2 and failure rules), and the studentised reprojection errors (mcba_observation_covariance).  Returns struct(cov
+    [C,F,B,P,2,2] (cov=True), student [C,F,B,P] (student=True), cam_max_std [C], trace (sum of the inliers' leverages = p_free),
+    sigma2, dof); NaN where the prediction is not constrained, 0 at invalid slots."""
+    from .structs import struct
+    x = self._x(x)
+    hold_u8 = None
+    if hold is not None:
+      hold_u8 = _u8(np.asarray(hold).astype(bool))
+      assert hold_u8.shape == (self.n_params,), f"hold mask of length {hold_u8.size}, expected {self.n_params}"
+    shape = tuple(self.shape)
+    pc = np.empty(shape + (3,)) if cov else None
+    st = np.empty(shape) if student else None
+    cam = np.empty(shape[0])
+    s2, dof, tr = C.c_double(), C.c_int64(), C.c_double()
+    opt = lambda a: None if a is None else _ptr(a, C.c_double)
+    check(self.lib.mcba_observation_covariance(self.h, _ptr(x, C.c_double), None if hold_u8 is None else _ptr(hold_u8, C.c_uint8),
+                                               0.0 if sigma2 is None else float(sigma2), opt(pc), opt(st), _ptr(cam, C.c_double),
+                                               C.byref(s2), C.byref(dof), C.byref(tr)))
+    out = struct(cam_max_std=cam, trace=tr.value, sigma2=s2.value, dof=dof.value)
+    if cov:
+      out = out._extend(cov=pc[..., [0, 1, 1, 2]].reshape(shape + (2, 2)))
+    if student:
+      out = out._extend(student=st)
+    return out
+
+  def set_observation_covariance_route(self, sigma_route):
+    """tests: force the Sigma-route fallback of observation_covariance (True) or restore the automatic choice (False)."""
+    check(self.lib.mcba_debug_set_observation_covariance_route(self.h, 1 if sigma_route else 0))
+
+  def observation_covariance_ms(self):
+    """HIP-event time of the per-observation pass of the last observation_covariance call (profiling aid)."""
+    ms = C.c_double()
+    check(self.lib.mcba_debug_observation_covariance_ms(self.h, C.byref(ms)))
+    return ms.value
+
   def debug_gn_step(self, reg):
     gn = np.empty(self.n_params)
     gh = np.empty(self.n_params)

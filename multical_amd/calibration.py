@@ -578,6 +578,53 @@ class Calibration(parameters.Parameters):
         parts.append(f"pose std rotation={np.degrees(np.linalg.norm(p[:3])):.4f} deg translation={np.linalg.norm(p[3:]):.5f}")
       info(" ".join(parts))
 
+  # --- prediction uncertainty per observation -----------------------------------------------------
+  def _observation_covariance(self, hold, sigma2, cov, student):
+    from . import gauge
+    held = gauge.default_hold(self) if hold is None else np.asarray(hold).astype(bool)
+    return self._handle().observation_covariance(self.param_vec, hold=held, sigma2=sigma2, cov=cov, student=student)
+
+  def prediction_covariance(self, hold=None, sigma2=None):
+    """Covariance of the predicted image point of every valid table slot, C_i = J_i Sigma J_i^T with Sigma of `covariance`
+    (same hold / sigma2): struct(cov [C,F,B,P,2,2], valid, sigma2, dof).  NaN where the prediction is not constrained (a valid
+    point whose frame, camera or board has no inlier).  Always the plain (unsharded) handle."""
+    oc = self._observation_covariance(hold, sigma2, True, False)
+    return struct(cov=oc.cov, valid=self.valid, sigma2=oc.sigma2, dof=oc.dof)
+
+  def studentized_error(self, hold=None, sigma2=None):
+    """Reprojection error of every valid point in units of its own standard deviation: d = sqrt(r^T Omega^-1 r) with Omega =
+    sigma2 I - C_i for inliers (residual covariance) and sigma2 I + C_i for the other valid points (prediction-error
+    covariance); d^2 is chi-square with 2 degrees of freedom under the model.  struct(error [C,F,B,P], valid)."""
+    oc = self._observation_covariance(hold, sigma2, False, True)
+    return struct(error=oc.student, valid=self.valid)
+
+  def reject_outliers_studentized(self, threshold, hold=None):
+    """The analogue of reject_outliers on the studentised error: inliers = valid points with d < threshold (NaN, an
+    unconstrained prediction, is rejected)."""
+    st = self.studentized_error(hold=hold)
+    with np.errstate(invalid="ignore"):
+      inliers = (st.error < threshold) & st.valid
+    n_in, n_valid = int(inliers.sum()), int(st.valid.sum())
+    info(f"Rejecting {n_valid - n_in} outliers with studentized error > {threshold:.2f}, "
+         f"keeping {n_in} / {n_valid} inliers, ({100.0 * n_in / max(n_valid, 1):.2f}%)")
+    return self.copy(inlier_mask=inliers)
+
+  def report_prediction_uncertainty(self, stage="", hold=None):
+    """One line per camera through the "calibration" logger: median and max standard deviation of the predicted points (px,
+    sqrt of the larger eigenvalue of C_i over the camera's valid points) and the largest leverage tr(H_ii) of its inliers."""
+    oc = self._observation_covariance(hold, None, True, False)
+    uu, uv, vv = oc.cov[..., 0, 0], oc.cov[..., 0, 1], oc.cov[..., 1, 1]
+    with np.errstate(invalid="ignore"):
+      std = np.sqrt(np.maximum(0.5 * (uu + vv) + np.sqrt((0.5 * (uu - vv)) ** 2 + uv ** 2), 0.0))
+    lev = (uu + vv) / oc.sigma2
+    names = getattr(self.camera_poses, "names", None) or [f"cam{i}" for i in range(self.size.cameras)]
+    for c in range(self.size.cameras):
+      s = std[c][self.valid[c] & np.isfinite(std[c])]
+      l = lev[c][self.inliers[c] & np.isfinite(lev[c])]
+      med = float(np.median(s)) if s.size else float("nan")
+      info(f"{stage} {names[c]}: predicted std median={med:.4f} max={float(oc.cam_max_std[c]):.4f} px, "
+           f"max leverage={float(l.max()) if l.size else float('nan'):.4f}")
+
 
 def split_std(calib, std):
   """A vector over calib.param_vec (standard deviations) split into the enabled blocks: camera_poses [C, 6], board_poses

@@ -33,6 +33,7 @@
 #include "mcba_lower.h"
 #include "mcba_solver_kernels.h"
 #include "mcba_cov_kernels.h"
+#include "mcba_obscov_kernels.h"
 #include "mcba_init_kernels.h"
 
 using namespace mcba;
@@ -336,6 +337,12 @@ struct mcba_handle_s {
   // system, its SYRK partials, Sigma_ss scaled (padded) and unscaled, per-frame blocks and cross blocks, pivot report
   DevBuf<double> cov_d, cov_zero, cov_x, cov_p, cov_sg, cov_sout, cov_ff, cov_fs;
   DevBuf<int32_t> cov_bad;
+  // mcba_observation_covariance: unobserved-and-not-held flags, [C,F,B,P,3] / [C,F,B,P] outputs, per-view {trace, max std} partials,
+  // {trace | per-camera max std}; HIP-event time of the last pass (k_obscov + k_obscov_fold)
+  DevBuf<uint8_t> oc_flag;
+  DevBuf<double> oc_cov, oc_student, oc_part, oc_out, oc_g;   // oc_g: Q [views][DF + ns][NG] of k_obscov_whiten
+  double oc_pass_ms = 0.0;
+  bool oc_sigma_route = false;   // debug (mcba_debug_set_observation_covariance_route): force the Sigma-route fallback (tests)
   int lin_grid = 0;          // 0 = automatic (see lin2), > 0 = forced number of persistent workgroups (debug)
 
   int64_t n_inliers = 0;               // inliers of this shard
@@ -2033,11 +2040,22 @@ int32_t mcba_covariance_layout(mcba_handle h, int32_t* n_shared, int32_t* df, in
   API_END
 }
 
-int32_t mcba_covariance(mcba_handle h, const double* x, const uint8_t* hold, double sigma2, double* cov_shared,
-                        double* cov_frames, double* cov_frame_shared, double* std_out, double* sigma2_out, int64_t* dof_out) {
-  API_BEGIN
-  REQUIRE(h && x, "null argument");
-  g_fill_stream = h->stream;
+namespace {
+
+// What the covariance chain leaves behind on the host; on the device: cov_sout (sigma^2 D Sigma_ss D, internal shared order),
+// cov_ff [Fl][DF][DF], cov_fs [Fl][DF][ns] (want_fs), cov_d (D).
+struct CovChain {
+  std::vector<int32_t> i2e;    // internal index -> caller index
+  std::vector<double> D;       // diag(H)^-1/2 of the free, observed parameters, else 0
+  std::vector<uint8_t> held;
+  double s2 = 0.0;             // the sigma^2 used
+  int64_t dof = 0, p_free = 0;
+  bool want_fs = false;
+};
+
+// Sigma = sigma^2 (J^T J)^-1 at x in block form on the device: shared by mcba_covariance and
+// mcba_observation_covariance.  Enqueued on the handle's stream; the last kernels have not been waited for on return.
+void covariance_chain(mcba_handle_s* h, const double* x, const uint8_t* hold, double sigma2, bool cross, CovChain& cc) {
   const Dims& d = h->d;
   REQUIRE(d.shard_world == 0 && d.f0 == 0 && d.Fl == d.F, "covariance: a frame-sharded handle is not supported (use a plain handle)");
   REQUIRE(d.ns + 1 <= CHOLP_MAX_N1, "covariance: the reduced system has " + std::to_string(d.ns) + " shared parameters; at most " +
@@ -2056,9 +2074,12 @@ int32_t mcba_covariance(mcba_handle h, const double* x, const uint8_t* hold, dou
   const double* diag = h->h_gbuf + n;
   const double cost = h->h_gbuf[2 * (size_t)n];
   // D = diag(H)^-1/2 of the free, observed parameters; 0 for held (hold[i] != 0) and unobserved (diag(H) == 0) ones
-  const std::vector<int32_t> i2e = int_to_ext(h);
-  std::vector<double> D((size_t)n, 0.0);
-  std::vector<uint8_t> held((size_t)n, 0);
+  cc.i2e = int_to_ext(h);
+  cc.D.assign((size_t)n, 0.0);
+  cc.held.assign((size_t)n, 0);
+  const std::vector<int32_t>& i2e = cc.i2e;
+  std::vector<double>& D = cc.D;
+  std::vector<uint8_t>& held = cc.held;
   int64_t p_free = 0;
   for (int k = 0; k < n; ++k) {
     held[k] = (hold != nullptr && i2e[k] >= 0 && hold[i2e[k]] != 0) ? 1 : 0;
@@ -2071,6 +2092,9 @@ int32_t mcba_covariance(mcba_handle h, const double* x, const uint8_t* hold, dou
   REQUIRE(dof > 0, "covariance: " + std::to_string(m) + " residuals do not determine " + std::to_string(p_free) +
                        " free parameters (m <= p_free)");
   const double s2 = sigma2 > 0.0 ? sigma2 : 2.0 * cost / (double)dof;
+  cc.s2 = s2;
+  cc.dof = dof;
+  cc.p_free = p_free;
   h->cov_d.alloc((size_t)n, false);
   h->cov_zero.alloc((size_t)n, false);
   HIP_OK(hipMemcpyAsync(h->cov_d.p, D.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -2119,7 +2143,8 @@ int32_t mcba_covariance(mcba_handle h, const double* x, const uint8_t* hold, dou
   hipLaunchKernelGGL(k_cov_fold, dim3(std::min(2048, (nsp * nsp + 255) / 256)), dim3(256), 0, h->stream, d, (const double*)h->cov_p.p,
                      ntile_s, COV_KSPLIT, (const double*)h->cov_d.p, s2, nsp, h->cov_sg.p, h->cov_sout.p);
   // per-frame marginal blocks (+ cross blocks)
-  const bool want_fs = cov_frame_shared != nullptr && K > 0;
+  const bool want_fs = cross && K > 0;
+  cc.want_fs = want_fs;
   if (K > 0) {
     h->cov_ff.alloc((size_t)K * DF, false);
     if (want_fs) h->cov_fs.alloc((size_t)K * ns, false);
@@ -2136,6 +2161,25 @@ int32_t mcba_covariance(mcba_handle h, const double* x, const uint8_t* hold, dou
     }
   }
   check_launch("covariance kernels");
+}
+
+}  // namespace
+
+int32_t mcba_covariance(mcba_handle h, const double* x, const uint8_t* hold, double sigma2, double* cov_shared,
+                        double* cov_frames, double* cov_frame_shared, double* std_out, double* sigma2_out, int64_t* dof_out) {
+  API_BEGIN
+  REQUIRE(h && x, "null argument");
+  g_fill_stream = h->stream;
+  const Dims& d = h->d;
+  CovChain cc;
+  covariance_chain(h, x, hold, sigma2, cov_frame_shared != nullptr, cc);
+  const int n = d.n, ns = d.ns, DF = d.DF, Fl = d.Fl, K = DF * Fl;
+  const bool want_fs = cc.want_fs;
+  const std::vector<int32_t>& i2e = cc.i2e;
+  const std::vector<double>& D = cc.D;
+  const std::vector<uint8_t>& held = cc.held;
+  const double s2 = cc.s2;
+  const int64_t dof = cc.dof;
   // downloads; rows / columns of the shared block in the caller's order
   std::vector<double> sout((size_t)ns * ns), ff((size_t)K * DF), fsv(want_fs ? (size_t)K * ns : 0);
   HIP_OK(hipMemcpyAsync(sout.data(), h->cov_sout.p, sout.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2165,6 +2209,78 @@ int32_t mcba_covariance(mcba_handle h, const double* x, const uint8_t* hold, dou
   }
   if (sigma2_out) *sigma2_out = s2;
   if (dof_out) *dof_out = dof;
+  API_END
+}
+
+int32_t mcba_observation_covariance(mcba_handle h, const double* x, const uint8_t* hold, double sigma2, double* pred_cov,
+                                    double* student, double* cam_max_std, double* sigma2_out, int64_t* dof_out, double* trace_out) {
+  API_BEGIN
+  REQUIRE(h && x, "null argument");
+  g_fill_stream = h->stream;
+  const Dims& d = h->d;
+  REQUIRE(d.shard_world == 0 && d.f0 == 0 && d.Fl == d.F,
+          "observation covariance: a frame-sharded handle is not supported (use a plain handle)");
+  REQUIRE(d.off_boards < 0, "observation covariance: the boards block is optimised (its " + std::to_string(d.n - d.off_boards) +
+                                " board-point parameters would join the shared system); not supported");
+  CovChain cc;
+  covariance_chain(h, x, hold, sigma2, true, cc);   // Sigma_ss, Sigma_ff and Sigma_fs stay on the device
+  const int n = d.n, nv = d.views();
+  // the view chains the point functions read, at x, for EVERY view (the pose / camera tables are those of the linearisation)
+  const int nvw = nv * (d.motion == MOTION_ROLLING ? 2 : 1);
+  if (nvw > 0) hipLaunchKernelGGL(k_views, dim3((nvw + 127) / 128), dim3(128), 0, h->stream, d, h->t);
+  // unobserved and not held: a slot whose row pair has a non-zero entry there is undetermined (NaN)
+  std::vector<uint8_t> flag((size_t)n);
+  for (int k = 0; k < n; ++k) flag[k] = (cc.D[k] == 0.0 && !cc.held[k]) ? 1 : 0;
+  h->oc_flag.alloc((size_t)n, false);
+  HIP_OK(hipMemcpyAsync(h->oc_flag.p, flag.data(), (size_t)n, hipMemcpyHostToDevice, h->stream));
+  const size_t nslot = (size_t)d.slots();
+  if (pred_cov) h->oc_cov.alloc(3 * nslot, false);
+  if (student) h->oc_student.alloc(nslot, false);
+  h->oc_part.alloc(2 * (size_t)std::max(nv, 1), false);
+  h->oc_out.alloc(1 + (size_t)d.C, false);
+  HIP_OK(hipMemsetAsync(h->oc_out.p, 0, (1 + (size_t)d.C) * sizeof(double), h->stream));
+  HIP_OK(hipEventRecord(h->ev0, h->stream));
+  // whitened route (Q per view, k_obscov_whiten) wherever the ns x NG panel fits the LDS of a workgroup and Q fits 8 GB; the
+  // Sigma-route beyond
+  constexpr int OCW_THREADS = 256;
+  const size_t lds_w = obscov_whiten_lds_bytes(d), nq = (size_t)(d.DF + d.ns) * (d.DE + d.KI);
+  const bool whiten = !h->oc_sigma_route && lds_w <= 150 * 1024 && nv > 0 && d.DE + d.KI <= OCW_THREADS && (size_t)nv * nq <= ((size_t)1 << 30);
+  if (whiten) {
+    h->oc_g.alloc((size_t)nv * nq, false);
+    raise_dynamic_lds((const void*)k_obscov_whiten<OCW_THREADS>, h->device, lds_w);
+    hipLaunchKernelGGL((k_obscov_whiten<OCW_THREADS>), dim3(nv), dim3(OCW_THREADS), lds_w, h->stream, d, h->t, (const double*)h->cov_d.p,
+                       (const double*)h->Lf.p, (const double*)h->W.p, (const double*)h->cov_x.p, h->oc_g.p);
+  }
+  h->ops->obs_cov(d, h->t, h->stream, h->cov_sout.p, h->cov_ff.p, h->cov_fs.p, h->oc_flag.p, cc.s2, pred_cov ? h->oc_cov.p : nullptr,
+                  student ? h->oc_student.p : nullptr, h->oc_part.p, h->oc_out.p, whiten ? (const double*)h->oc_g.p : nullptr);
+  HIP_OK(hipEventRecord(h->ev1, h->stream));
+  check_launch("observation covariance kernels");
+  std::vector<double> out(1 + (size_t)d.C);
+  if (pred_cov) HIP_OK(hipMemcpyAsync(pred_cov, h->oc_cov.p, 3 * nslot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (student) HIP_OK(hipMemcpyAsync(student, h->oc_student.p, nslot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipMemcpyAsync(out.data(), h->oc_out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  sync(h);
+  float ms = 0.f;
+  HIP_OK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->oc_pass_ms = (double)ms;
+  if (cam_max_std) std::copy(out.begin() + 1, out.end(), cam_max_std);
+  if (trace_out) *trace_out = out[0];
+  if (sigma2_out) *sigma2_out = cc.s2;
+  if (dof_out) *dof_out = cc.dof;
+  API_END
+}
+
+int32_t mcba_debug_set_observation_covariance_route(mcba_handle h, int32_t sigma_route) {
+  API_BEGIN
+  REQUIRE(h, "null handle");
+  h->oc_sigma_route = sigma_route != 0;
+  API_END
+}
+
+int32_t mcba_debug_observation_covariance_ms(mcba_handle h, double* ms) {
+  API_BEGIN
+  REQUIRE(h && ms, "null argument");
+  *ms = h->oc_pass_ms;
   API_END
 }
 

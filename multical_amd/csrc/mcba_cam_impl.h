@@ -1,6 +1,7 @@
 // mcba_cam_impl.h -- body of one camera-model translation unit: define MCBA_ND, MCBA_FISH, MCBA_CAM_FN, include.
 #include <algorithm>
 #include "mcba_kernels.h"
+#include "mcba_obscov_kernels.h"
 #include "mcba_camops.h"
 
 namespace mcba {
@@ -206,7 +207,25 @@ void lsmr_fused2(MCBA_F2_ARGS) {
 #undef MCBA_F2_ARGS
 #undef MCBA_F2_PASS
 
-const CamOps OPS = {residual, project_model, cost, jacobian, linearize, points, lsmr_jv, lsmr_jtu, lsmr_fused, lsmr_fused2};
+template <int MOTION>
+void oc1(const Dims& d, const Tables& t, hipStream_t s, const double* Sss, const double* Sff, const double* Sfs, const uint8_t* pflag,
+         double sigma2, double* pred_cov, double* student, double* vpart, int nblk, const double* gview) {
+  if (d.KI > 0)
+    hipLaunchKernelGGL((k_obscov<ND_, FISH_, MOTION, true>), dim3(nblk), dim3(64), 0, s, d, t, Sss, Sff, Sfs, pflag, sigma2, pred_cov, student, vpart, gview);
+  else
+    hipLaunchKernelGGL((k_obscov<ND_, FISH_, MOTION, false>), dim3(nblk), dim3(64), 0, s, d, t, Sss, Sff, Sfs, pflag, sigma2, pred_cov, student, vpart, gview);
+}
+void obs_cov(const Dims& d, const Tables& t, hipStream_t s, const double* Sss, const double* Sff, const double* Sfs, const uint8_t* pflag,
+             double sigma2, double* pred_cov, double* student, double* vpart, double* out, const double* gview) {
+  if (d.views() == 0) return;
+  const int nblk = std::min(d.views(), 16384);   // single-wave workgroups, views dealt round-robin
+  if (d.motion == MOTION_STATIC) oc1<MOTION_STATIC>(d, t, s, Sss, Sff, Sfs, pflag, sigma2, pred_cov, student, vpart, nblk, gview);
+  else if (d.motion == MOTION_ROLLING) oc1<MOTION_ROLLING>(d, t, s, Sss, Sff, Sfs, pflag, sigma2, pred_cov, student, vpart, nblk, gview);
+  else oc1<MOTION_HAND_EYE>(d, t, s, Sss, Sff, Sfs, pflag, sigma2, pred_cov, student, vpart, nblk, gview);
+  hipLaunchKernelGGL((k_obscov_fold<1024>), dim3(1 + d.C), dim3(1024), 0, s, d, (const double*)vpart, out);
+}
+
+const CamOps OPS = {residual, project_model, cost, jacobian, linearize, points, lsmr_jv, lsmr_jtu, lsmr_fused, lsmr_fused2, obs_cov};
 
 }  // namespace
 

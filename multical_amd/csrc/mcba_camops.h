@@ -35,6 +35,11 @@ struct CamOps {
   void (*lsmr_fused2)(const Dims&, const Tables&, hipStream_t, const int32_t* first, const double* dscale, const double* v, double* u,
                       double* partial, double* xpart, double* part, int part_stride, double* bpart, int nblk, const double* lsIn,
                       double* lsOut, const double* vpart, int nv, double* hbar, double* x, double* h, double* cache, int mode, LsmrCompact cp);
+  // per-observation prediction covariance (mcba_obscov_kernels.h): k_obscov over every view, then k_obscov_fold -> out[1 + C] =
+  // {trace, per-camera max std}.  Sss / Sff / Sfs: the covariance blocks on the device; pflag[n]: unobserved and not held
+  void (*obs_cov)(const Dims&, const Tables&, hipStream_t, const double* Sss, const double* Sff, const double* Sfs,
+                  const uint8_t* pflag, double sigma2, double* pred_cov, double* student, double* vpart, double* out,
+                  const double* gview /* Q [views][DF + ns][NG] of k_obscov_whiten, or null: the Sigma-route */);
 };
 
 const CamOps* cam_ops_pin4();

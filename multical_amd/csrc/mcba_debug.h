@@ -70,6 +70,11 @@ int32_t mcba_debug_set_lsmr_masks_form(mcba_handle h, int32_t on);
 int32_t mcba_debug_set_allreduce_trace(mcba_handle h, int32_t cap);
 /* persistent workgroups of the LSMR product kernels (default 2048): summation-order experiments                                 */
 int32_t mcba_debug_set_lsmr_grid(mcba_handle h, int32_t grid);
+/* HIP-event time (ms) of the per-observation pass alone (k_obscov + k_obscov_fold) in the last mcba_observation_covariance      */
+int32_t mcba_debug_observation_covariance_ms(mcba_handle h, double* ms);
+/* 1: mcba_observation_covariance takes the Sigma-route (G = That Sigma_view That^T per view), the fallback of systems whose
+ * whitened panel does not fit LDS, on every rig (tests); 0 (default): automatic                                                  */
+int32_t mcba_debug_set_observation_covariance_route(mcba_handle h, int32_t sigma_route);
 
 #ifdef __cplusplus
 }
