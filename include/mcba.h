@@ -371,6 +371,41 @@ int32_t mcba_align_poses_indexed(int32_t n_problems, const int64_t* offsets, con
                                  const uint8_t* mask, double threshold, int32_t invert, double* out, uint8_t* out_valid,
                                  uint8_t* inliers);
 
+/* --- per-view board poses: the pose table tables.make_pose_table builds (tables.py:44-66) ------------------------ */
+/* One board pose per (camera, frame, board) view from its detections: board.estimate_pose_points (board/common.py:36-47:
+ * camera.undistort_points, then cv2.solvePnPGeneric with K and no distortion) for every view of the table in one launch
+ * (csrc/mcba_pnp.h: exact undistortion by Newton's method, planar homography start, Levenberg-Marquardt to convergence on
+ * sum |K pi(R X + t) - K (x, y, 1)|^2 in pixels).  Handle-less like mcba_align_poses_*.                                  */
+#define MCBA_VIEW_OK 0             /* pose, sse and n_used are those of the converged optimum                          */
+#define MCBA_VIEW_TOO_FEW 1        /* fewer than 4 usable corners (after corners that do not undistort are dropped)     */
+#define MCBA_VIEW_MASKED 2         /* view_mask[view] == 0                                                             */
+#define MCBA_VIEW_DEGENERATE 3     /* no homography: corners collinear or coincident                                   */
+#define MCBA_VIEW_NOT_CONVERGED 4  /* the step test was not met within max_iterations (the last iterate is returned)   */
+typedef struct mcba_view_pose_problem {
+  int32_t C, F, B, P;             /* cameras, frames, boards, padded corners per board                                 */
+  const double* points;           /* [C,F,B,P,2] detected corners (pixels)                                             */
+  const uint8_t* valid;           /* [C,F,B,P]                                                                         */
+  const double* board_points;     /* [B,P,3] board geometry, padded                                                    */
+  const int32_t* board_sizes;     /* [B] corners of every board (the rest of P is padding), or NULL = P                */
+  const double* cameras;          /* [C, 5 + n_dist] parameter blocks [fx fy cx cy skew dist...] (camera.py:144-171)    */
+  int32_t n_dist;                 /* width of the dist part of every block                                             */
+  const int32_t* camera_n_dist;   /* [C] coefficients each camera really has (4, 5, 8, 12 or 14), or NULL = n_dist      */
+  const uint8_t* is_fisheye;      /* [C] Kannala-Brandt (4 coefficients) instead of Brown-Conrady, or NULL = none       */
+  const uint8_t* fix_aspect;      /* [C] fy = fx (camera.py:159-160), or NULL = none                                    */
+  const uint8_t* view_mask;       /* [C,F,B] views to estimate (has_min_detections), or NULL = every view; views with   */
+                                  /* fewer than 4 corners are never estimated                                          */
+  const double* init_poses;       /* [C,F,B,4,4] start of the refinement, or NULL = planar homography start; required   */
+                                  /* for a board whose points are not coplanar                                         */
+  int32_t max_iterations;         /* Levenberg-Marquardt linearisations per view; <= 0: 50                              */
+  int32_t* lm_iterations;         /* OUT [C,F,B] linearisations used, or NULL                                          */
+} mcba_view_pose_problem;
+/* poses [C,F,B,4,4] board -> camera; sse [C,F,B] sum of squared pixel distances at the optimum (raw: no error norm is baked
+ * in); n_used [C,F,B] corners that entered; status [C,F,B] MCBA_VIEW_*.  Views without a pose: identity, sse 0, n_used 0.  */
+int32_t mcba_view_poses(const mcba_view_pose_problem* p, double* poses, double* sse, int32_t* n_used, uint8_t* status);
+/* timing of the last mcba_view_poses call of this thread, milliseconds: [0] host preparation + compaction of the active views,
+ * [1] uploads, [2] kernel, [3] downloads + scatter; *n_active (or NULL) = views launched                               */
+int32_t mcba_debug_view_poses_ms(double* ms /*[4]*/, int64_t* n_active);
+
 /* --- solve -------------------------------------------------------------------------------------------------- */
 /* Trust-region least squares: replaces scipy.optimize.least_squares(method='trf', x_scale='jac', jac_sparsity=S,
  * loss, f_scale, ftol, max_nfev) at calibration.py:209-210.  x is updated in place to `res.x`.                 */

@@ -50,25 +50,29 @@ class Board(Parameters):
 
 class CharucoBoard(Board):
   def __init__(self, size=None, square_length=None, marker_length=None, adjusted_points=None, points=None, name=None,
-               **ignored):
+               min_rows=3, min_points=20, **ignored):
     self.size = None if size is None else tuple(size)
     self.square_length, self.marker_length = square_length, marker_length
+    self.min_rows, self.min_points = min_rows, min_points   # board/charuco.py:12: has_min_detections (tables.min_detections_mask)
     pts = points if points is not None else synthetic.charuco_points(self.size, square_length)
     super().__init__(pts, adjusted_points, name)
 
   def __getstate__(self):
     return dict(size=self.size, square_length=self.square_length, marker_length=self.marker_length,
-                adjusted_points=self.adjusted_points, points=self._points, name=self.name)
+                adjusted_points=self.adjusted_points, points=self._points, name=self.name, min_rows=self.min_rows,
+                min_points=self.min_points)
 
 
 class AprilGrid(Board):
   def __init__(self, size=None, tag_length=None, tag_spacing=None, adjusted_points=None, points=None, name=None,
-               **ignored):
+               min_rows=2, min_points=12, **ignored):
     self.size = None if size is None else tuple(size)
     self.tag_length, self.tag_spacing = tag_length, tag_spacing
+    self.min_rows, self.min_points = min_rows, min_points   # board/aprilgrid.py:26
     pts = points if points is not None else synthetic.aprilgrid_points(self.size, tag_length, tag_spacing)
     super().__init__(pts, adjusted_points, name)
 
   def __getstate__(self):
     return dict(size=self.size, tag_length=self.tag_length, tag_spacing=self.tag_spacing,
-                adjusted_points=self.adjusted_points, points=self._points, name=self.name)
+                adjusted_points=self.adjusted_points, points=self._points, name=self.name, min_rows=self.min_rows,
+                min_points=self.min_points)

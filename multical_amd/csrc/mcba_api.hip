@@ -35,6 +35,8 @@
 #include "mcba_cov_kernels.h"
 #include "mcba_obscov_kernels.h"
 #include "mcba_init_kernels.h"
+#include "mcba_pnp_kernels.h"
+#include "mcba_pnp_driver.h"
 
 using namespace mcba;
 
@@ -1943,6 +1945,129 @@ int32_t mcba_align_poses_indexed(int32_t n_problems, const int64_t* offsets, con
   API_BEGIN
   REQUIRE(index_a && index_b, "null index list");
   align_poses(n_problems, offsets, table_a, n_a, index_a, table_b, n_b, index_b, mask, threshold, invert, out, out_valid, inliers);
+  API_END
+}
+
+// ---- per-view board poses (csrc/mcba_pnp.h, k_view_pose) ----------------------------------------------------------------
+namespace {
+thread_local double g_view_pose_ms[4] = {0.0, 0.0, 0.0, 0.0};
+thread_local int64_t g_view_pose_active = 0;
+
+void view_poses(const mcba_view_pose_problem& p, double* poses, double* sse, int32_t* n_used, uint8_t* status) {
+  const double t0 = now_seconds();
+  pnp::ViewPlan plan;
+  std::string err;
+  if (!pnp::plan_views(p, plan, err)) throw Error(err);
+  REQUIRE(pnp::view_pose_npl(p.P) > 0, "mcba_view_poses: boards of more than 1024 corners are not served");
+  pnp::fill_invalid(p, plan, poses, sse, n_used, status);
+  const size_t na = plan.active.size(), P = (size_t)p.P;
+  g_view_pose_active = (int64_t)na;
+  for (double& v : g_view_pose_ms) v = 0.0;
+  if (na == 0) {                       // nothing to estimate: nothing is launched, the device is not touched
+    g_view_pose_ms[0] = (now_seconds() - t0) * 1e3;
+    return;
+  }
+  hipStream_t st = resource_cache().take_stream();
+  if (st == nullptr) HIP_OK(hipStreamCreate(&st));
+  struct StreamGuard {
+    hipStream_t s;
+    ~StreamGuard() {
+      if (!resource_cache().park_stream(s)) (void)hipStreamDestroy(s);
+    }
+  } guard{st};
+  g_fill_stream = st;
+  struct ParkReset { ~ParkReset() { g_park_on_release = false; } } park_reset;   // (declared first: runs after the buffers went)
+  // the rows of the ACTIVE views only, gathered into pinned memory: the table is about 0.3 full, and a pinned source is copied
+  // without the runtime's staging pass
+  const size_t px_bytes = na * P * 2 * sizeof(double), ok_bytes = na * P, in_bytes = p.init_poses ? na * 16 * sizeof(double) : 0;
+  const size_t stage_bytes = px_bytes + in_bytes + ok_bytes;
+  char* stage = (char*)pinned_alloc(stage_bytes);
+  struct PinGuard { void* q; size_t n; ~PinGuard() { pinned_free(q, n); } } pin_guard{stage, stage_bytes};
+  double* h_px = (double*)stage;
+  double* h_in = (double*)(stage + px_bytes);
+  uint8_t* h_ok = (uint8_t*)(stage + px_bytes + in_bytes);
+  for (size_t k = 0; k < na; ++k) {
+    const size_t v = (size_t)plan.active[k];
+    memcpy(h_px + k * P * 2, p.points + v * P * 2, P * 2 * sizeof(double));
+    memcpy(h_ok + k * P, p.valid + v * P, P);
+    if (p.init_poses) memcpy(h_in + k * 16, p.init_poses + v * 16, 16 * sizeof(double));
+  }
+  DevBuf<double> d_px, d_in, d_board, d_cam, d_planes, d_out;
+  DevBuf<uint8_t> d_ok, d_fish, d_status;
+  DevBuf<int32_t> d_desc, d_nd, d_int;
+  d_px.alloc(na * P * 2, false);
+  d_ok.alloc(na * P, false);
+  if (p.init_poses) d_in.alloc(na * 16, false);
+  d_board.alloc((size_t)p.B * P * 3, false);
+  d_cam.alloc(plan.cam.size(), false);
+  d_planes.alloc(plan.planes.size(), false);
+  d_desc.alloc(2 * na, false);
+  d_nd.alloc((size_t)p.C, false);
+  d_fish.alloc((size_t)p.C, false);
+  d_out.alloc(na * 17, false);          // pose [na][16] | sse [na]
+  d_int.alloc(na * 2, false);           // n_used [na] | iterations [na]
+  d_status.alloc(na, false);
+  const double t1 = now_seconds();
+  HIP_OK(hipMemcpyAsync(d_px.p, h_px, px_bytes, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_ok.p, h_ok, ok_bytes, hipMemcpyHostToDevice, st));
+  if (p.init_poses) HIP_OK(hipMemcpyAsync(d_in.p, h_in, in_bytes, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_board.p, p.board_points, (size_t)p.B * P * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_cam.p, plan.cam.data(), plan.cam.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_planes.p, plan.planes.data(), plan.planes.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_desc.p, plan.desc.data(), 2 * na * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_nd.p, plan.cam_nd.data(), (size_t)p.C * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_fish.p, plan.cam_fish.data(), (size_t)p.C, hipMemcpyHostToDevice, st));
+  HIP_OK(hipStreamSynchronize(st));
+  const double t2 = now_seconds();
+  pnp::ViewPoseArgs a;
+  a.n_active = (int)na; a.P = p.P; a.max_iter = plan.max_iter;
+  a.pixel = d_px.p; a.valid = d_ok.p; a.desc = d_desc.p; a.init = p.init_poses ? d_in.p : nullptr; a.board = d_board.p;
+  a.cam = d_cam.p; a.cam_nd = d_nd.p; a.cam_fish = d_fish.p; a.planes = d_planes.p;
+  a.pose = d_out.p; a.sse = d_out.p + na * 16; a.n_used = d_int.p; a.iters = d_int.p + na; a.status = d_status.p;
+  pnp::view_pose_launch(a, st);
+  check_launch("k_view_pose");
+  HIP_OK(hipStreamSynchronize(st));
+  const double t3 = now_seconds();
+  std::vector<double> h_out(na * 17);
+  std::vector<int32_t> h_int(na * 2);
+  std::vector<uint8_t> h_status(na);
+  HIP_OK(hipMemcpyAsync(h_out.data(), d_out.p, na * 17 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(h_int.data(), d_int.p, na * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(h_status.data(), d_status.p, na, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  for (size_t k = 0; k < na; ++k) {
+    const size_t v = (size_t)plan.active[k];
+    memcpy(poses + v * 16, h_out.data() + k * 16, 16 * sizeof(double));
+    sse[v] = h_out[na * 16 + k];
+    n_used[v] = h_int[k];
+    status[v] = h_status[k];
+    if (p.lm_iterations) p.lm_iterations[v] = h_int[na + k];
+  }
+  const double t4 = now_seconds();
+  g_view_pose_ms[0] = (t1 - t0) * 1e3;
+  g_view_pose_ms[1] = (t2 - t1) * 1e3;
+  g_view_pose_ms[2] = (t3 - t2) * 1e3;
+  g_view_pose_ms[3] = (t4 - t3) * 1e3;
+  if (getenv("MCBA_TIMING"))
+    fprintf(stderr, "[view_poses] %lld of %lld views, %d corners a row: plan + gather %.2f ms, uploads (%.1f MB) %.2f ms, kernel %.2f ms, "
+            "downloads + scatter %.2f ms\n", (long long)na, (long long)plan.status.size(), p.P, g_view_pose_ms[0],
+            (double)(stage_bytes) / 1e6, g_view_pose_ms[1], g_view_pose_ms[2], g_view_pose_ms[3]);
+  g_park_on_release = true;   // regular end: the buffers of this scope are parked for the next call of the same shape
+}
+}  // namespace
+
+int32_t mcba_view_poses(const mcba_view_pose_problem* p, double* poses, double* sse, int32_t* n_used, uint8_t* status) {
+  API_BEGIN
+  REQUIRE(p && poses && sse && n_used && status, "null argument");
+  view_poses(*p, poses, sse, n_used, status);
+  API_END
+}
+
+int32_t mcba_debug_view_poses_ms(double* ms, int64_t* n_active) {
+  API_BEGIN
+  REQUIRE(ms, "null argument");
+  for (int i = 0; i < 4; ++i) ms[i] = g_view_pose_ms[i];
+  if (n_active) *n_active = g_view_pose_active;
   API_END
 }
 

@@ -9,6 +9,9 @@ mean.  Here all alignments of a stage run as ONE batch on the device (mcba_align
 what stays on the host is the control logic on tiny arrays -- the overlap matrix, the greedy spanning tree
 (graph.select_pairs, graph.py:7-33), chaining the pair transforms along the tree -- and 4x4 matrix products.
 
+The pose table itself -- one board pose per (camera, frame, board) view, `make_pose_table` (tables.py:44-66) -- is estimated on
+the device as well: mcba_view_poses runs board.estimate_pose_points (undistort + solvePnP) for every view in one launch.
+
 Tables are `structs.Table`s with `poses [..., 4, 4]`, `valid [...]` (+ `num_points` for the pose table), like the
 reference's.  `make_point_table` (tables.py:68-81) is data marshalling of ragged detections and stays in numpy.
 """
@@ -266,3 +269,148 @@ def make_point_table(detections, boards):
     points[image, point] = np.concatenate([a.reshape(-1, 2) for a, i in zip(corners, ids) if i.size]).astype(dtype, copy=False)
     valid[image, point] = True
   return Table.create(points=points.reshape(C_, F, B, num_points, 2), valid=valid.reshape(C_, F, B, num_points))
+
+
+# ---- the pose table: one board pose per view from its detections (tables.py:38-66, board/common.py:30-47) -----------------
+VIEW_OK, VIEW_TOO_FEW, VIEW_MASKED, VIEW_DEGENERATE, VIEW_NOT_CONVERGED = 0, 1, 2, 3, 4   # mcba.h: MCBA_VIEW_*
+
+
+def _is_fisheye(camera):
+  return type(camera).__name__ == "CameraFisheye" or getattr(camera, "model", None) == "fisheye"
+
+
+class ViewPoseInputs(object):
+  """The arrays of one mcba_view_pose_problem, kept alive next to the ctypes struct that points into them."""
+
+  def __init__(self, points, valid, board_points, cameras, view_mask=None, init_poses=None, max_iterations=0, board_sizes=None):
+    self.points = _f64(points)
+    self.valid = np.ascontiguousarray(np.asarray(valid).astype(np.uint8))
+    self.shape = self.valid.shape[:3]
+    C_, F, B = self.shape
+    P = self.valid.shape[3]
+    assert self.points.shape == (C_, F, B, P, 2) and len(cameras) == C_ and len(board_points) == B
+    self.board_sizes = np.ascontiguousarray(np.array([len(b) for b in board_points] if board_sizes is None else board_sizes,
+                                                     dtype=np.int32))
+    self.board_points = np.zeros((B, P, 3))
+    for b, pts in enumerate(board_points):
+      self.board_points[b, :len(pts)] = np.asarray(pts, dtype=np.float64)
+    # camera blocks [fx fy cx cy skew dist...]: the INTRINSIC MATRIX as it is -- estimate_pose_points hands cv2 camera.intrinsic,
+    # not the fix_aspect parameterisation of the bundle adjustment (board/common.py:42)
+    nds = [int(np.asarray(c.dist).size) for c in cameras]
+    self.n_dist = max(nds + [4])
+    self.cameras = np.zeros((C_, 5 + self.n_dist))
+    for i, c in enumerate(cameras):
+      K = np.asarray(c.intrinsic, dtype=np.float64)
+      self.cameras[i, :5] = [K[0, 0], K[1, 1], K[0, 2], K[1, 2], K[0, 1]]
+      self.cameras[i, 5:5 + nds[i]] = np.asarray(c.dist, dtype=np.float64).ravel()
+    self.camera_n_dist = np.ascontiguousarray(np.array(nds, dtype=np.int32))
+    self.is_fisheye = np.ascontiguousarray(np.array([_is_fisheye(c) for c in cameras], dtype=np.uint8))
+    self.view_mask = None if view_mask is None else np.ascontiguousarray(np.asarray(view_mask).astype(np.uint8))
+    self.init_poses = None if init_poses is None else _f64(init_poses)
+    assert self.view_mask is None or self.view_mask.shape == self.shape
+    assert self.init_poses is None or self.init_poses.shape == self.shape + (4, 4)
+    self.max_iterations = int(max_iterations)
+    self.lm_iterations = np.zeros(self.shape, dtype=np.int32)
+
+  def struct(self):
+    dp, up, ip = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+    s = _lib.ViewPoseProblem()
+    s.C, s.F, s.B = self.shape
+    s.P = self.valid.shape[3]
+    s.points, s.valid = self.points.ctypes.data_as(dp), self.valid.ctypes.data_as(up)
+    s.board_points, s.board_sizes = self.board_points.ctypes.data_as(dp), self.board_sizes.ctypes.data_as(ip)
+    s.cameras, s.n_dist = self.cameras.ctypes.data_as(dp), self.n_dist
+    s.camera_n_dist, s.is_fisheye = self.camera_n_dist.ctypes.data_as(ip), self.is_fisheye.ctypes.data_as(up)
+    s.fix_aspect = None
+    s.view_mask = None if self.view_mask is None else self.view_mask.ctypes.data_as(up)
+    s.init_poses = None if self.init_poses is None else self.init_poses.ctypes.data_as(dp)
+    s.max_iterations = self.max_iterations
+    s.lm_iterations = self.lm_iterations.ctypes.data_as(ip)
+    return s
+
+  def outputs(self):
+    return (np.empty(self.shape + (4, 4)), np.empty(self.shape), np.empty(self.shape, dtype=np.int32),
+            np.empty(self.shape, dtype=np.uint8))
+
+
+def view_poses(points, valid, board_points, cameras, view_mask=None, init_poses=None, max_iterations=0):
+  """mcba_view_poses: (poses [C,F,B,4,4], sse [C,F,B], n_used, status, lm_iterations) of every view of the detection table;
+  board_points: one [P_b, 3] array per board.  Views that are masked out or hold fewer than 4 corners are not launched."""
+  inp = ViewPoseInputs(points, valid, board_points, cameras, view_mask, init_poses, max_iterations)
+  poses, sse, n_used, status = inp.outputs()
+  s = inp.struct()
+  dp = C.POINTER(C.c_double)
+  check(_lib.load().mcba_view_poses(C.byref(s), poses.ctypes.data_as(dp), sse.ctypes.data_as(dp),
+                                    n_used.ctypes.data_as(C.POINTER(C.c_int32)), status.ctypes.data_as(C.POINTER(C.c_uint8))))
+  return poses, sse, n_used, status, inp.lm_iterations
+
+
+def min_detections_mask(valid, boards):
+  """board.has_min_detections of every view [C, F, B] (has_min_detections_grid, board/common.py:30-34), vectorised: integer work on
+  the ids.  The ids of a view are the indices of its valid corners (tables.sparse_points); they are unravelled over (h, w) of the
+  board's `size` -- as the reference does, also for a charuco board whose corners form an (h-1) x (w-1) grid -- and an AprilGrid
+  tests the TAG ids `ids // 4` (board/aprilgrid.py:197-199) while its count stays the number of corners.  `size`, `min_rows`,
+  `min_points` are read from the board objects by duck typing; a board without them (a bare point set) passes every view."""
+  valid = np.asarray(valid).astype(bool)
+  C_, F, B, P = valid.shape
+  mask = np.ones((C_, F, B), dtype=bool)
+  for b, board in enumerate(boards):
+    size, min_rows, min_points = (getattr(board, k, None) for k in ("size", "min_rows", "min_points"))
+    if size is None or min_rows is None or min_points is None:
+      continue
+    w, h = int(size[0]), int(size[1])
+    n = min(P, int(board.num_points)) if hasattr(board, "num_points") else P
+    ids = np.arange(n)
+    if type(board).__name__ == "AprilGrid" or hasattr(board, "tag_length"):
+      ids = ids // 4
+    if n > 0 and int(ids.max()) >= h * w:
+      raise ValueError(f"board {b}: ids beyond its {h} x {w} grid")     # (np.unravel_index raises in the reference)
+    v = valid[:, :, b, :n].reshape(-1, n).astype(np.float32)
+    rows = (v @ (ids[:, None] // w == np.arange(h)[None]).astype(np.float32) > 0).sum(axis=1)
+    cols = (v @ (ids[:, None] % w == np.arange(w)[None]).astype(np.float32) > 0).sum(axis=1)
+    count = valid[:, :, b, :n].reshape(-1, n).sum(axis=1)
+    mask[:, :, b] = ((count >= min_points) & (rows >= min_rows) & (cols >= min_rows)).reshape(C_, F)
+  return mask
+
+
+def make_pose_table(point_table, boards, cameras, exclude_bad_poses=True, pose_error_limit=1.0, error_norm='point',
+                    return_info=False):
+  """tables.make_pose_table (tables.py:44-66): the board pose of every (camera, frame, board) view from its detections, all views in
+  ONE device call (mcba_view_poses) instead of one cv2.solvePnPGeneric per view.  Returns the reference's table -- poses [C,F,B,4,4],
+  valid, num_points, reprojection_error, view_angles [C,F,B,3] -- whose invalid entries are tables.invalid_pose (identity, 0, 0,
+  [0, 0, 0]); it feeds `initialise_poses` unchanged.
+
+  A view is estimated when it passes board.has_min_detections (`min_detections_mask`) and holds 4 corners.  It is valid when the
+  estimate converged (status 0) and -- with exclude_bad_poses -- its reprojection_error does not exceed pose_error_limit.
+
+  error_norm: 'point' -> sqrt(sse / n), the RMS distance per corner (the convention synthetic.view_pose_errors states);
+  'coordinate' -> sqrt(sse / 2n), the RMS per coordinate.  OpenCV's solvePnPGeneric is believed to report the latter
+  (norm / sqrt(2 N)); that could not be checked -- no cv2 on the machines this was built on -- so the default stays with the
+  project's own convention and the choice is the caller's.  The two differ by exactly sqrt(2).
+
+  Deviations from the reference's numbers, by construction: the undistortion is the exact inverse of the projection,
+  not cv2's five fixed-point sweeps; points stay float64; the refinement is iterated to the optimum, not to cv2's stop.
+
+  return_info: also return struct(status, sse, num_used, error, lm_iterations, view_mask) over [C,F,B] (error: before invalid
+  entries are zeroed)."""
+  if error_norm not in ('point', 'coordinate'):
+    raise ValueError(f"error_norm {error_norm!r}: 'point' or 'coordinate'")
+  valid_pts = np.asarray(point_table.valid).astype(bool)
+  view_mask = min_detections_mask(valid_pts, boards)
+  poses, sse, n_used, status, iters = view_poses(point_table.points, valid_pts, [np.asarray(b.points) for b in boards], cameras,
+                                                 view_mask=view_mask)
+  per = 1.0 if error_norm == 'point' else 2.0
+  error = np.sqrt(sse / (per * np.maximum(n_used, 1)))
+  valid = status == VIEW_OK
+  if exclude_bad_poses:
+    valid = valid & (error <= pose_error_limit)
+  from scipy.spatial.transform import Rotation
+  angles = np.zeros(valid.shape + (3,))
+  if valid.any():
+    angles[valid] = Rotation.from_matrix(poses[valid][:, :3, :3]).as_euler('xyz', degrees=True)   # transform/rtvec.py:55-58
+  table = Table.create(poses=np.where(valid[..., None, None], poses, np.eye(4)), valid=valid,
+                       num_points=np.where(valid, valid_pts.sum(axis=3), 0),
+                       reprojection_error=np.where(valid, error, 0.0), view_angles=angles)
+  if return_info:
+    return table, struct(status=status, sse=sse, num_used=n_used, error=error, lm_iterations=iters, view_mask=view_mask)
+  return table

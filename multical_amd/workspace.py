@@ -1,10 +1,17 @@
 """Minimal mirror of multical.workspace.Workspace for the optimisation phase only (workspace.py:228-247).
 
-Image loading, detection, intrinsic calibration, pose initialisation, export and the pickle checkpoint are upstream /
-downstream of the hot path and stay with the reference; a Workspace here is seeded with an
-initial Calibration and reproduces `calibrate`'s enable -> adjust_outliers sequence and argument mapping.
+Image loading, detection, intrinsic calibration, export and the pickle checkpoint are upstream / downstream of the hot path and
+stay with the reference; a Workspace here is seeded with an initial Calibration -- given, or
+built from a detection table by `initialise_poses` (workspace.py:196-226) on the device -- and reproduces `calibrate`'s
+enable -> adjust_outliers sequence and argument mapping.
 """
+import numpy as np
+
+from . import tables
 from .calibration import Calibration, select_threshold
+from .motion import StaticFrames
+from .parameters import ParamList
+from .pose_set import PoseSet
 
 
 class Workspace(object):
@@ -21,6 +28,25 @@ class Workspace(object):
   @property
   def latest_calibration(self) -> Calibration:
     return list(self.calibrations.values())[-1]
+
+  def initialise_poses(self, point_table, boards, cameras, motion_model=StaticFrames, camera_poses=None, exclude_bad_poses=True,
+                       pose_error_limit=1.0, names=None) -> Calibration:
+    """workspace.py:196-226 from a detection table: per-view board poses (tables.make_pose_table), the pose-graph initialisation
+    (tables.initialise_poses) and the initial Calibration, stored as calibrations["initialisation"].  camera_poses: {camera name:
+    4x4} like the reference's, or an array [C, 4, 4]; names: struct(camera, board, image) of name lists (default: cam0, ...)."""
+    C_, F, B = np.asarray(point_table.valid).shape[:3]
+    cam_names = list(names.camera) if names is not None else [f"cam{i}" for i in range(C_)]
+    board_names = list(names.board) if names is not None else [f"board{i}" for i in range(B)]
+    image_names = list(names.image) if names is not None else [f"frame{i}" for i in range(F)]
+    self.pose_table = tables.make_pose_table(point_table, boards, cameras, exclude_bad_poses, pose_error_limit)
+    if isinstance(camera_poses, dict):
+      camera_poses = np.array([camera_poses[k] for k in cam_names])
+    pose_init = tables.initialise_poses(self.pose_table, camera_poses=camera_poses)
+    calib = Calibration(ParamList(cameras, cam_names), ParamList(boards, board_names), point_table,
+                        PoseSet(pose_init.camera, cam_names), PoseSet(pose_init.board, board_names),
+                        motion_model.init(pose_init.times, image_names))
+    self.calibrations["initialisation"] = calib
+    return calib
 
   def calibrate(self, name="calibration", camera_poses=True, motion=True, board_poses=True, cameras=False, boards=False,
                 loss='linear', tolerance=1e-4, num_adjustments=3, quantile=0.75, auto_scale=None,
