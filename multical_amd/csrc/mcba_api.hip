@@ -30,6 +30,7 @@
 #include "../../include/mcba.h"
 #include "mcba_debug.h"
 #include "mcba_camops.h"
+#include "mcba_dispatch.h"
 #include "mcba_lower.h"
 #include "mcba_solver_kernels.h"
 #include "mcba_cov_kernels.h"
@@ -345,7 +346,7 @@ struct mcba_handle_s {
   DevBuf<double> oc_cov, oc_student, oc_part, oc_out, oc_g;   // oc_g: Q [views][DF + ns][NG] of k_obscov_whiten
   double oc_pass_ms = 0.0;
   bool oc_sigma_route = false;   // debug (mcba_debug_set_observation_covariance_route): force the Sigma-route fallback (tests)
-  int lin_grid = 0;          // 0 = automatic (see lin2), > 0 = forced number of persistent workgroups (debug)
+  int lin_grid = 0;          // 0 = automatic (see linearize, mcba_cam_impl.h), > 0 = forced number of persistent workgroups (debug)
 
   int64_t n_inliers = 0;               // inliers of this shard
   int64_t n_evalid = 0;                // points in the mask of tables.reprojection_error (this shard)
@@ -940,12 +941,10 @@ void launch_gn_solve(mcba_handle_s* h, double reg, bool root_rank, double* dots_
                        trp->Delta);
   if (K > 0) {
     const TrRegPartials z = trp ? *trp : TrRegPartials{nullptr, 0, nullptr, 0, 0, 0.0};
-    if (d.DF == 12)
-      hipLaunchKernelGGL((k_schur_frame<12>), dim3(d.Fl), dim3(256), 0, h->stream, d, h->Hff.p, h->Hfs.p, h->dsc.p, h->gh.p, reg,
+    with_df(d.DF, [&](auto df) {
+      hipLaunchKernelGGL((k_schur_frame<df>), dim3(d.Fl), dim3(256), 0, h->stream, d, h->Hff.p, h->Hfs.p, h->dsc.p, h->gh.p, reg,
                          h->Lf.p, h->W.p, h->yf.p, tr_dev, z.vs, z.nvb, z.q, z.nq, z.first, z.Delta);
-    else
-      hipLaunchKernelGGL((k_schur_frame<6>), dim3(d.Fl), dim3(256), 0, h->stream, d, h->Hff.p, h->Hfs.p, h->dsc.p, h->gh.p, reg,
-                         h->Lf.p, h->W.p, h->yf.p, tr_dev, z.vs, z.nvb, z.q, z.nq, z.first, z.Delta);
+    });
     launch_schur_syrk(h, K);
   }
   const int total = d.ns * d.ns + d.ns;
@@ -954,15 +953,11 @@ void launch_gn_solve(mcba_handle_s* h, double reg, bool root_rank, double* dots_
   call_allreduce(h, h->sbuf.p, (size_t)total, 0);
   launch_chol(h, d.ns, tr_dev ? 0.0 : reg, h->sbuf.p, h->ps.p);
   check_launch("reduced Cholesky");
-  if (d.DF == 12) {
+  with_df(d.DF, [&](auto df) {
     const int nblk = gn_dot_blocks(d);
-    hipLaunchKernelGGL((k_schur_backsub<12>), dim3(nblk), dim3(64), 0, h->stream, d, h->Lf.p, h->W.p, h->yf.p, h->ps.p,
+    hipLaunchKernelGGL((k_schur_backsub<df>), dim3(nblk), dim3(64), 0, h->stream, d, h->Lf.p, h->W.p, h->yf.p, h->ps.p,
                        h->gn.p, h->gh.p, h->info.p, fused_dots);
-  } else {
-    const int nblk = gn_dot_blocks(d);
-    hipLaunchKernelGGL((k_schur_backsub<6>), dim3(nblk), dim3(64), 0, h->stream, d, h->Lf.p, h->W.p, h->yf.p, h->ps.p,
-                       h->gn.p, h->gh.p, h->info.p, fused_dots);
-  }
+  });
   if (h->allreduce && dots_out) {   // message 4: 3 doubles per rank (+ the pivot report), gathered by summation
     const int W = d.shard_world;
     hipLaunchKernelGGL(k_shard_fold_dots, dim3(1), dim3(64), 0, h->stream, dots_out, gn_dot_blocks(d), d.shard_rank, W,
@@ -2226,12 +2221,10 @@ void covariance_chain(mcba_handle_s* h, const double* x, const uint8_t* hold, do
   HIP_OK(hipMemsetAsync(h->cov_zero.p, 0, (size_t)n * sizeof(double), h->stream));
   // frame blocks and the reduced system in the scaled space, no damping, unit diagonal where D = 0
   if (K > 0) {
-    if (DF == 12)
-      hipLaunchKernelGGL((k_schur_frame<12, true>), dim3(Fl), dim3(256), 0, h->stream, d, h->Hff.p, h->Hfs.p, h->cov_d.p, h->cov_zero.p,
+    with_df(DF, [&](auto df) {
+      hipLaunchKernelGGL((k_schur_frame<df, true>), dim3(Fl), dim3(256), 0, h->stream, d, h->Hff.p, h->Hfs.p, h->cov_d.p, h->cov_zero.p,
                          0.0, h->Lf.p, h->W.p, h->yf.p, (double*)nullptr, (const double*)nullptr, 0, (const double*)nullptr, 0, 0, 0.0);
-    else
-      hipLaunchKernelGGL((k_schur_frame<6, true>), dim3(Fl), dim3(256), 0, h->stream, d, h->Hff.p, h->Hfs.p, h->cov_d.p, h->cov_zero.p,
-                         0.0, h->Lf.p, h->W.p, h->yf.p, (double*)nullptr, (const double*)nullptr, 0, (const double*)nullptr, 0, 0, 0.0);
+    });
     launch_schur_syrk(h, K);
   }
   const int total = ns * ns + ns;
@@ -2275,15 +2268,11 @@ void covariance_chain(mcba_handle_s* h, const double* x, const uint8_t* hold, do
     if (want_fs) h->cov_fs.alloc((size_t)K * ns, false);
     const size_t lds_f = cov_frame_lds_bytes(nsp);
     double* fs = want_fs ? h->cov_fs.p : nullptr;
-    if (DF == 12) {
-      raise_dynamic_lds((const void*)k_cov_frame<12>, h->device, lds_f);
-      hipLaunchKernelGGL((k_cov_frame<12>), dim3(Fl), dim3(COV_FRAME_THREADS), lds_f, h->stream, d, (const double*)h->Lf.p,
+    with_df(DF, [&](auto df) {
+      raise_dynamic_lds((const void*)k_cov_frame<df>, h->device, lds_f);
+      hipLaunchKernelGGL((k_cov_frame<df>), dim3(Fl), dim3(COV_FRAME_THREADS), lds_f, h->stream, d, (const double*)h->Lf.p,
                          (const double*)h->W.p, (const double*)h->cov_sg.p, nsp, (const double*)h->cov_d.p, s2, h->cov_ff.p, fs);
-    } else {
-      raise_dynamic_lds((const void*)k_cov_frame<6>, h->device, lds_f);
-      hipLaunchKernelGGL((k_cov_frame<6>), dim3(Fl), dim3(COV_FRAME_THREADS), lds_f, h->stream, d, (const double*)h->Lf.p,
-                         (const double*)h->W.p, (const double*)h->cov_sg.p, nsp, (const double*)h->cov_d.p, s2, h->cov_ff.p, fs);
-    }
+    });
   }
   check_launch("covariance kernels");
 }

@@ -196,6 +196,122 @@ __device__ __forceinline__ double wave_fold_batched(const double* __restrict__ a
 // slots: masks of a segment are compacted, its dense chunks are processed, and the accumulators / the residual run of the
 // view carry on into the next segment.  Point indices are kept as uint16 (mcba_create checks n_points <= 65535).
 constexpr int LIN_MAX_POINTS = 512;
+constexpr int NPB64 = LIN_MAX_POINTS / 64;   // 64-lane groups of a segment
+
+// ---------------------------------------------------------------------------------------------------------------
+// The idioms of the per-view walk, each said ONCE: k_residual, k_cost and k_lsmr_jv / jtu / fused are composed of them.  All are
+// inlined into the calling kernel; LDS arrays stay __shared__ in the kernel and arrive as pointers.  Every floating-point
+// statement stands here whole (-ffp-contract=on contracts within one statement): none may be split over a helper and its caller.
+// k_lsmr_fused2 and k_linearize take their sizes from ViewShape but say the other idioms in their own words: moved into these
+// functions, the same statements change the register allocation and the instruction order of those two kernels
+// (profiles/view_idioms_isa.txt), and their code objects are not to move with a refactoring.  A change to an idiom is made here
+// AND in those two kernels.
+// ---------------------------------------------------------------------------------------------------------------
+// sizes that follow from the motion model and the intrinsics block of a camera-model translation unit
+template <int ND, int MOTION, bool OPTK>
+struct ViewShape {
+  static constexpr bool ROLL = MOTION == MOTION_ROLLING;
+  static constexpr int DE = ROLL ? 12 : 6;                    // columns of E: one or two chain poses
+  static constexpr int NPB = MOTION == MOTION_STATIC ? 3 : 4;   // pose blocks of a view
+  static constexpr int NPC = 6 * NPB;                         // pose columns of That
+  static constexpr int KI = OPTK ? 4 + ND : 0;                // optimised intrinsics
+  static constexpr int NS = DE + KI, NV = NS + 1;             // row of an observation: [E | K] (+ the residual)
+};
+
+// mask bytes of segment seg0 of a view's row (one byte per lane and 64-lane group), then their ballot compaction into the
+// point list pidx (slot order); returns the number of inliers.  The list is in LDS: lds_fence() before it is read.
+__device__ __forceinline__ void load_inlier_bytes(const uint8_t* row, int seg0, int P, int lane, uint8_t (&inb)[NPB64]) {
+#pragma unroll
+  for (int k = 0; k < NPB64; ++k) inb[k] = masked_load_row(row, seg0 + k * 64 + lane, P);
+}
+__device__ __forceinline__ int compact_inlier_bytes(const uint8_t (&inb)[NPB64], int seg0, int lane, uint16_t* pidx) {
+  int count = 0;
+#pragma unroll
+  for (int k = 0; k < NPB64; ++k) {
+    const bool in = inb[k] != 0;
+    const unsigned long long m = __ballot(in);
+    if (in) pidx[count + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(seg0 + k * 64 + lane);
+    count += __popcll(m);
+  }
+  return count;
+}
+// both steps back to back, list ready to read.  (The halves stay separate functions although this is their only caller today:
+//  k_lsmr_fused2 and k_linearize request the bytes early and compact them later, in their own words for now -- see above -- and a
+//  later move of those kernels onto the helpers needs exactly this split.)
+__device__ __forceinline__ int inlier_list(const Dims& d, const Tables& t, int v, int seg0, int lane, uint16_t* pidx) {
+  uint8_t inb[NPB64];
+  load_inlier_bytes(t.inlier + (size_t)v * d.P, seg0, d.P, lane, inb);
+  const int count = compact_inlier_bytes(inb, seg0, lane, pidx);
+  lds_fence();
+  return count;
+}
+
+// request of the first chunk behind a compaction: point index, observation and board point of this lane
+__device__ __forceinline__ void first_chunk(const Dims& d, const Tables& t, int v, int b, int count, int lane, const uint16_t* pidx,
+                                            int& p_cur, double2& ob_cur, double (&X_cur)[3]) {
+  p_cur = lane < count ? pidx[lane] : 0;
+  ob_cur = t.obs[(size_t)v * d.P + p_cur];
+  for (int k = 0; k < 3; ++k) X_cur[k] = t.board_points[3 * (size_t)(b * d.P + p_cur) + k];
+}
+
+// The view's direction wl = [That (D v)_pose | (D v)_intrinsics]: lane i < NPC + KI stages (D v)[local_to_x(i)] -- pose entries
+// into vp, intrinsics into wl[DE ..) --, then lane a < DE forms wl[a] = sum_j That[a][j] vp[j] from the view's That (k_tmat's table)
+template <class VS>
+__device__ __forceinline__ void view_direction(const Dims& d, const Tables& t, int v, int f, int c, int b, int lane,
+                                               const double* dscale, const double* vin, double* vp, double* wl) {
+  if (lane < VS::NPC + VS::KI) {
+    const int xi = local_to_x(d, f, c, b, lane);
+    const double val = xi >= 0 ? dscale[xi] * vin[xi] : 0.0;
+    if (lane < VS::NPC) vp[lane] = val; else wl[VS::DE + lane - VS::NPC] = val;
+  }
+  lds_fence();
+  if (lane < VS::DE) {
+    const double* Tm = t.tmat + (size_t)v * (VS::DE * VS::NPC) + lane * VS::NPC;
+    double sum = 0.0;
+#pragma unroll
+    for (int j = 0; j < VS::NPC; ++j) sum += Tm[j] * vp[j];
+    wl[lane] = sum;
+  }
+  lds_fence();
+}
+
+// adjoint epilogue of a view: lane i writes entry i of [That^T sl[0 .. DE) | sl[DE ..)] to out[i]
+template <class VS>
+__device__ __forceinline__ void view_adjoint(const double* That, const double* sl, int lane, double* out) {
+  if (lane < VS::NPC) {
+    double sum = 0.0;
+#pragma unroll
+    for (int a = 0; a < VS::DE; ++a) sum += That[a * VS::NPC + lane] * sl[a];
+    out[lane] = sum;
+  } else if (lane < VS::NPC + VS::KI) {
+    out[lane] = sl[VS::DE + lane - VS::NPC];
+  }
+}
+
+// adjusted board points (boards=True): the term  jp . (D v)[point]  of the two rows of observation p, jp = rs A R_view, and its
+// adjoint  jp^T (ox, oy)  (3 doubles, summed per point by the gather).  bterm stays as it is without a board block.
+template <int ND, bool ROLL>
+__device__ __forceinline__ void board_term(const Dims& d, const Tables& t, int v, int b, int p, const PointState<ND, ROLL>& ps,
+                                           const double* dscale, const double* vin, double (&bterm)[2]) {
+  if (d.off_boards >= 0) {
+    const int gq = d.off_boards + 3 * (t.board_off[b] + p);
+    double w3[3];
+    board_point_direction<ROLL>(t, v, ps.tr, dscale[gq] * vin[gq], dscale[gq + 1] * vin[gq + 1], dscale[gq + 2] * vin[gq + 2], w3);
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+      bterm[a] = ps.rs[a] * (ps.A[3 * a] * w3[0] + ps.A[3 * a + 1] * w3[1] + ps.A[3 * a + 2] * w3[2]);
+  }
+}
+template <int ND, bool ROLL>
+__device__ __forceinline__ void board_adjoint(const Tables& t, int v, const PointState<ND, ROLL>& ps, double ox, double oy,
+                                              double* out3) {
+  double q3[3], w3[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) q3[k] = ps.rs[0] * ox * ps.A[k] + ps.rs[1] * oy * ps.A[3 + k];
+  board_point_adjoint<ROLL>(t, v, ps.tr, q3, w3);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out3[k] = w3[k];
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // k_residual: evaluate() of optimization/calibration.py:204-206 (+ projections and per-slot errors of
@@ -222,28 +338,16 @@ __global__ __launch_bounds__(256) void k_residual(Dims d, Tables t, const int32_
     __shared__ uint16_t plist[4][LIN_MAX_POINTS];
     uint16_t* pidx = plist[threadIdx.x >> 6];
     const int n_active = t.active_views[0];
-    constexpr int NPB64 = LIN_MAX_POINTS / 64;
     for (int vi = blockIdx.x * 4 + (threadIdx.x >> 6); vi < n_active; vi += gridDim.x * 4) {
       const int v = __builtin_amdgcn_readfirstlane(t.active_views[1 + vi]);
       const int b = v % d.B, c = (v / d.B) % d.C;
       size_t out0 = (size_t)first[v];
       for (int seg0 = 0; seg0 < d.P; seg0 += LIN_MAX_POINTS) {   // (one segment unless a board has > LIN_MAX_POINTS points)
-      uint8_t inb[NPB64];
-#pragma unroll
-      for (int k = 0; k < NPB64; ++k) inb[k] = masked_load_row(t.inlier + (size_t)v * d.P, seg0 + k * 64 + lane, d.P);
-      int count = 0;
-#pragma unroll
-      for (int k = 0; k < NPB64; ++k) {
-        const bool in = inb[k] != 0;
-        const unsigned long long m = __ballot(in);
-        if (in) pidx[count + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(seg0 + k * 64 + lane);
-        count += __popcll(m);
-      }
-      lds_fence();
-      int p_cur = lane < count ? pidx[lane] : 0;
-      double2 ob_cur = t.obs[(size_t)v * d.P + p_cur];
+      const int count = inlier_list(d, t, v, seg0, lane, pidx);
+      int p_cur;
+      double2 ob_cur;
       double X_cur[3], X_nxt[3];
-      for (int k = 0; k < 3; ++k) X_cur[k] = t.board_points[3 * (size_t)(b * d.P + p_cur) + k];
+      first_chunk(d, t, v, b, count, lane, pidx, p_cur, ob_cur, X_cur);
       for (int base = 0; base < count; base += 64) {
         const int i = base + lane, inx = i + 64;
         const int p_nxt = inx < count ? pidx[inx] : p_cur;
@@ -440,28 +544,13 @@ __global__ __launch_bounds__(64) void k_cost(Dims d, Tables t, double* __restric
     // the chain matrices of the view straight from the pose table (wave-uniform work, done by every lane): a trial step
     // then needs k_prep only, not the per-view table pass k_views
     view_chain_wave<ROLL>(d, t, f, c, b, lane, Vtmp, Vc);
-    constexpr int NPB64 = LIN_MAX_POINTS / 64;
     for (int seg0 = 0; seg0 < d.P; seg0 += LIN_MAX_POINTS) {   // (one segment unless a board has > LIN_MAX_POINTS points)
-    uint8_t inb[NPB64];
-#pragma unroll
-    for (int k = 0; k < NPB64; ++k) {
-      const int p = seg0 + k * 64 + lane;
-      inb[k] = masked_load_row(t.inlier + (size_t)v * d.P, p, d.P);
-    }
-    int count = 0;
-#pragma unroll
-    for (int k = 0; k < NPB64; ++k) {
-      const bool in = inb[k] != 0;
-      const unsigned long long m = __ballot(in);
-      if (in) pidx[count + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(seg0 + k * 64 + lane);
-      count += __popcll(m);
-    }
-    lds_fence();
-    // observation + board point of the NEXT chunk are requested before the current one is evaluated (as in k_linearize)
-    int p_cur = lane < count ? pidx[lane] : 0;
-    double2 ob_cur = t.obs[(size_t)v * d.P + p_cur];
+    const int count = inlier_list(d, t, v, seg0, lane, pidx);
+    // observation + board point of the NEXT chunk are requested before the current one is evaluated (first_chunk, then one ahead)
+    int p_cur;
+    double2 ob_cur;
     double X_cur[3], X_nxt[3];
-    for (int k = 0; k < 3; ++k) X_cur[k] = t.board_points[3 * (size_t)(b * d.P + p_cur) + k];
+    first_chunk(d, t, v, b, count, lane, pidx, p_cur, ob_cur, X_cur);
     for (int base = 0; base < count; base += 64) {
       const int i = base + lane, inx = i + 64;
       const int p_nxt = inx < count ? pidx[inx] : p_cur;
@@ -504,9 +593,9 @@ __global__ __launch_bounds__(64) void k_lsmr_jv(Dims d, Tables t, const int32_t*
                                                 const double* __restrict__ dscale, const double* __restrict__ vin, double alpha,
                                                 double* __restrict__ u, double* __restrict__ partial,
                                                 const double* __restrict__ ls = nullptr) {
-  constexpr bool ROLL = MOTION == MOTION_ROLLING;
-  constexpr int DE = ROLL ? 12 : 6, NPB = MOTION == MOTION_STATIC ? 3 : 4, NPC = 6 * NPB, KI = OPTK ? 4 + ND : 0;
-  constexpr int NV = DE + KI + 1;
+  using VS = ViewShape<ND, MOTION, OPTK>;
+  constexpr bool ROLL = VS::ROLL;
+  constexpr int DE = VS::DE, NPC = VS::NPC, KI = VS::KI, NV = VS::NV;
   __shared__ uint16_t pidx[LIN_MAX_POINTS];
   __shared__ double vp[NPC], wl[DE + KI + 1];
   const int lane = threadIdx.x;
@@ -520,37 +609,11 @@ __global__ __launch_bounds__(64) void k_lsmr_jv(Dims d, Tables t, const int32_t*
     const int v = t.active_views[1 + vi];
     if (v < 0) continue;
     const int b = v % d.B, c = (v / d.B) % d.C, f = d.f0 + v / (d.B * d.C);
-    if (mode != 1) {   // the view's scaled local parameter vector, then w = That vp
-      if (lane < NPC + KI) {
-        const int xi = local_to_x(d, f, c, b, lane);
-        const double val = xi >= 0 ? dscale[xi] * vin[xi] : 0.0;
-        if (lane < NPC) vp[lane] = val; else wl[DE + lane - NPC] = val;
-      }
-      lds_fence();
-      if (lane < DE) {
-        const double* Tm = t.tmat + (size_t)v * (DE * NPC) + lane * NPC;
-        double sum = 0.0;
-#pragma unroll
-        for (int j = 0; j < NPC; ++j) sum += Tm[j] * vp[j];
-        wl[lane] = sum;
-      }
-      lds_fence();
-    }
+    // the view's scaled local parameter vector, then w = That vp
+    if (mode != 1) view_direction<VS>(d, t, v, f, c, b, lane, dscale, vin, vp, wl);
     size_t out0 = (size_t)first[v];
-    constexpr int NPB64 = LIN_MAX_POINTS / 64;
     for (int seg0 = 0; seg0 < d.P; seg0 += LIN_MAX_POINTS) {
-      uint8_t inb[NPB64];
-#pragma unroll
-      for (int k = 0; k < NPB64; ++k) inb[k] = masked_load_row(t.inlier + (size_t)v * d.P, seg0 + k * 64 + lane, d.P);
-      int count = 0;
-#pragma unroll
-      for (int k = 0; k < NPB64; ++k) {
-        const bool in = inb[k] != 0;
-        const unsigned long long m = __ballot(in);
-        if (in) pidx[count + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(seg0 + k * 64 + lane);
-        count += __popcll(m);
-      }
-      lds_fence();
+      const int count = inlier_list(d, t, v, seg0, lane, pidx);
       for (int base = 0; base < count; base += 64) {
         const int i = base + lane;
         if (i < count) {
@@ -562,14 +625,7 @@ __global__ __launch_bounds__(64) void k_lsmr_jv(Dims d, Tables t, const int32_t*
           old.x = old.y = 0.0;
           if (mode == 0) old = reinterpret_cast<const double2*>(u)[out0 + i];
           double bterm[2] = {0.0, 0.0};
-          if (mode != 1 && d.off_boards >= 0) {   // adjusted board points (boards=True): + jp . (D v)[point], jp = rs A R_view
-            const int gq = d.off_boards + 3 * (t.board_off[b] + p);
-            double w3[3];
-            board_point_direction<ROLL>(t, v, ps.tr, dscale[gq] * vin[gq], dscale[gq + 1] * vin[gq + 1], dscale[gq + 2] * vin[gq + 2], w3);
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-              bterm[a] = ps.rs[a] * (ps.A[3 * a] * w3[0] + ps.A[3 * a + 1] * w3[1] + ps.A[3 * a + 2] * w3[2]);
-          }
+          if (mode != 1) board_term(d, t, v, b, p, ps, dscale, vin, bterm);   // adjusted board points (boards=True)
 #pragma unroll
           for (int a = 0; a < 2; ++a) {
             double row[NV];
@@ -603,9 +659,9 @@ template <int ND, int FISH, int MOTION, bool OPTK, bool ROBUST>
 __global__ __launch_bounds__(64) void k_lsmr_jtu(Dims d, Tables t, const int32_t* __restrict__ first, double inv_beta,
                                                  double* __restrict__ u, double* __restrict__ part, int part_stride,
                                                  double* __restrict__ bpart, const double* __restrict__ ls = nullptr) {
-  constexpr bool ROLL = MOTION == MOTION_ROLLING;
-  constexpr int DE = ROLL ? 12 : 6, NPB = MOTION == MOTION_STATIC ? 3 : 4, NPC = 6 * NPB, KI = OPTK ? 4 + ND : 0;
-  constexpr int NV = DE + KI + 1, NS = DE + KI;
+  using VS = ViewShape<ND, MOTION, OPTK>;
+  constexpr bool ROLL = VS::ROLL;
+  constexpr int DE = VS::DE, NPC = VS::NPC, NV = VS::NV, NS = VS::NS;
   __shared__ uint16_t pidx[LIN_MAX_POINTS];
   __shared__ double sl[NS];
   const int lane = threadIdx.x;
@@ -622,20 +678,8 @@ __global__ __launch_bounds__(64) void k_lsmr_jtu(Dims d, Tables t, const int32_t
 #pragma unroll
     for (int k = 0; k < NS; ++k) sums[k] = 0.0;
     size_t out0 = (size_t)first[v];
-    constexpr int NPB64 = LIN_MAX_POINTS / 64;
     for (int seg0 = 0; seg0 < d.P; seg0 += LIN_MAX_POINTS) {
-      uint8_t inb[NPB64];
-#pragma unroll
-      for (int k = 0; k < NPB64; ++k) inb[k] = masked_load_row(t.inlier + (size_t)v * d.P, seg0 + k * 64 + lane, d.P);
-      int count = 0;
-#pragma unroll
-      for (int k = 0; k < NPB64; ++k) {
-        const bool in = inb[k] != 0;
-        const unsigned long long m = __ballot(in);
-        if (in) pidx[count + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(seg0 + k * 64 + lane);
-        count += __popcll(m);
-      }
-      lds_fence();
+      const int count = inlier_list(d, t, v, seg0, lane, pidx);
       for (int base = 0; base < count; base += 64) {
         const int i = base + lane;
         if (i < count) {
@@ -646,14 +690,8 @@ __global__ __launch_bounds__(64) void k_lsmr_jtu(Dims d, Tables t, const int32_t
           uu.x *= inv_beta;
           uu.y *= inv_beta;
           reinterpret_cast<double2*>(u)[out0 + i] = uu;
-          if (bpart != nullptr) {   // boards=True: jp^T u of this observation (3 doubles, residual order), summed per point by k_lsmr_gather
-            double q3[3], w3[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) q3[k] = ps.rs[0] * uu.x * ps.A[k] + ps.rs[1] * uu.y * ps.A[3 + k];
-            board_point_adjoint<ROLL>(t, v, ps.tr, q3, w3);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) bpart[3 * (out0 + i) + k] = w3[k];
-          }
+          // boards=True: jp^T u of this observation (3 doubles, residual order), summed per point by k_lsmr_gather
+          if (bpart != nullptr) board_adjoint(t, v, ps, uu.x, uu.y, bpart + 3 * (out0 + i));
 #pragma unroll
           for (int a = 0; a < 2; ++a) {
             double row[NV];
@@ -673,16 +711,7 @@ __global__ __launch_bounds__(64) void k_lsmr_jtu(Dims d, Tables t, const int32_t
       if (lane == 0) sl[k] = tot;
     }
     lds_fence();
-    double* out = part + (size_t)v * part_stride;
-    if (lane < NPC) {
-      const double* Tm = t.tmat + (size_t)v * (DE * NPC);
-      double sum = 0.0;
-#pragma unroll
-      for (int a = 0; a < DE; ++a) sum += Tm[a * NPC + lane] * sl[a];
-      out[lane] = sum;
-    } else if (lane < NPC + KI) {
-      out[lane] = sl[DE + lane - NPC];
-    }
+    view_adjoint<VS>(t.tmat + (size_t)v * (DE * NPC), sl, lane, part + (size_t)v * part_stride);
     lds_fence();
   }
 }
@@ -703,9 +732,9 @@ __global__ __launch_bounds__(64) void k_lsmr_fused(Dims d, Tables t, const int32
                                                    double* __restrict__ u, double* __restrict__ partial,
                                                    double* __restrict__ part, int part_stride, double* __restrict__ bpart,
                                                    const double* __restrict__ ls) {
-  constexpr bool ROLL = MOTION == MOTION_ROLLING;
-  constexpr int DE = ROLL ? 12 : 6, NPB = MOTION == MOTION_STATIC ? 3 : 4, NPC = 6 * NPB, KI = OPTK ? 4 + ND : 0;
-  constexpr int NV = DE + KI + 1, NS = DE + KI;
+  using VS = ViewShape<ND, MOTION, OPTK>;
+  constexpr bool ROLL = VS::ROLL;
+  constexpr int DE = VS::DE, NPC = VS::NPC, NV = VS::NV, NS = VS::NS;
   __shared__ uint16_t pidx[LIN_MAX_POINTS];
   __shared__ double vp[NPC], wl[NS], sl[NS];
   const int lane = threadIdx.x;
@@ -718,38 +747,13 @@ __global__ __launch_bounds__(64) void k_lsmr_fused(Dims d, Tables t, const int32
     if (v < 0) continue;
     const int b = v % d.B, c = (v / d.B) % d.C, f = d.f0 + v / (d.B * d.C);
     // the view's scaled local parameter vector, then w = That vp
-    if (lane < NPC + KI) {
-      const int xi = local_to_x(d, f, c, b, lane);
-      const double val = xi >= 0 ? dscale[xi] * vin[xi] : 0.0;
-      if (lane < NPC) vp[lane] = val; else wl[DE + lane - NPC] = val;
-    }
-    lds_fence();
-    if (lane < DE) {
-      const double* Tm = t.tmat + (size_t)v * (DE * NPC) + lane * NPC;
-      double sum = 0.0;
-#pragma unroll
-      for (int j = 0; j < NPC; ++j) sum += Tm[j] * vp[j];
-      wl[lane] = sum;
-    }
-    lds_fence();
+    view_direction<VS>(d, t, v, f, c, b, lane, dscale, vin, vp, wl);
     double sums[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) sums[k] = 0.0;
     size_t out0 = (size_t)first[v];
-    constexpr int NPB64 = LIN_MAX_POINTS / 64;
     for (int seg0 = 0; seg0 < d.P; seg0 += LIN_MAX_POINTS) {
-      uint8_t inb[NPB64];
-#pragma unroll
-      for (int k = 0; k < NPB64; ++k) inb[k] = masked_load_row(t.inlier + (size_t)v * d.P, seg0 + k * 64 + lane, d.P);
-      int count = 0;
-#pragma unroll
-      for (int k = 0; k < NPB64; ++k) {
-        const bool in = inb[k] != 0;
-        const unsigned long long m = __ballot(in);
-        if (in) pidx[count + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(seg0 + k * 64 + lane);
-        count += __popcll(m);
-      }
-      lds_fence();
+      const int count = inlier_list(d, t, v, seg0, lane, pidx);
       for (int base = 0; base < count; base += 64) {
         const int i = base + lane;
         if (i < count) {
@@ -760,14 +764,7 @@ __global__ __launch_bounds__(64) void k_lsmr_fused(Dims d, Tables t, const int32
           old.x *= inv_beta_old;      // (the normalised u of the previous step, rounded as k_lsmr_jtu stored it)
           old.y *= inv_beta_old;
           double bterm[2] = {0.0, 0.0};
-          if (d.off_boards >= 0) {   // adjusted board points: + jp . (D v)[point]
-            const int gq = d.off_boards + 3 * (t.board_off[b] + p);
-            double w3[3];
-            board_point_direction<ROLL>(t, v, ps.tr, dscale[gq] * vin[gq], dscale[gq + 1] * vin[gq + 1], dscale[gq + 2] * vin[gq + 2], w3);
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-              bterm[a] = ps.rs[a] * (ps.A[3 * a] * w3[0] + ps.A[3 * a + 1] * w3[1] + ps.A[3 * a + 2] * w3[2]);
-          }
+          board_term(d, t, v, b, p, ps, dscale, vin, bterm);   // adjusted board points: + jp . (D v)[point]
           double2 o;
 #pragma unroll
           for (int a = 0; a < 2; ++a) {
@@ -784,14 +781,8 @@ __global__ __launch_bounds__(64) void k_lsmr_fused(Dims d, Tables t, const int32
           }
           reinterpret_cast<double2*>(u)[out0 + i] = o;
           acc += o.x * o.x + o.y * o.y;
-          if (bpart != nullptr) {   // boards=True: jp^T uhat of this observation (summed per point by the gather)
-            double q3[3], w3[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) q3[k] = ps.rs[0] * o.x * ps.A[k] + ps.rs[1] * o.y * ps.A[3 + k];
-            board_point_adjoint<ROLL>(t, v, ps.tr, q3, w3);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) bpart[3 * (out0 + i) + k] = w3[k];
-          }
+          // boards=True: jp^T uhat of this observation (summed per point by the gather)
+          if (bpart != nullptr) board_adjoint(t, v, ps, o.x, o.y, bpart + 3 * (out0 + i));
         }
       }
       out0 += (size_t)count;
@@ -804,16 +795,7 @@ __global__ __launch_bounds__(64) void k_lsmr_fused(Dims d, Tables t, const int32
     const double tot = wave_reduce_many<NS>(sums, lane);
     if (many_writer<NS>(lane)) sl[many_index(lane)] = tot;
     lds_fence();
-    double* out = part + (size_t)v * part_stride;
-    if (lane < NPC) {
-      const double* Tm = t.tmat + (size_t)v * (DE * NPC);
-      double sum = 0.0;
-#pragma unroll
-      for (int a = 0; a < DE; ++a) sum += Tm[a * NPC + lane] * sl[a];
-      out[lane] = sum;
-    } else if (lane < NPC + KI) {
-      out[lane] = sl[DE + lane - NPC];
-    }
+    view_adjoint<VS>(t.tmat + (size_t)v * (DE * NPC), sl, lane, part + (size_t)v * part_stride);
     lds_fence();
   }
   const double tot = wave_sum(acc);
@@ -870,10 +852,10 @@ __global__ __launch_bounds__(64) MCBA_F2_OCCUPANCY void k_lsmr_fused2(Dims d, Ta
                                                     const double* __restrict__ vpart, int nv, double* __restrict__ hbar,
                                                     double* __restrict__ xv, double* __restrict__ hv, double* __restrict__ cache,
                                                     LsmrCompact cp) {
-  constexpr bool ROLL = MOTION == MOTION_ROLLING;
+  using VS = ViewShape<ND, MOTION, OPTK>;
+  constexpr bool ROLL = VS::ROLL;
   constexpr bool DESC = MODE >= 2;          // the view list comes as descriptors {view, first, count}
-  constexpr int DE = ROLL ? 12 : 6, NPB = MOTION == MOTION_STATIC ? 3 : 4, NPC = 6 * NPB, KI = OPTK ? 4 + ND : 0;
-  constexpr int NS = DE + KI;
+  constexpr int DE = VS::DE, NPC = VS::NPC, KI = VS::KI, NS = VS::NS;
   using CL = LsmrCacheLayout<ROLL, ROBUST>;
   __shared__ uint16_t pidx[LIN_MAX_POINTS];
   __shared__ double vp[NPC], wl[NS], sl[NS];
@@ -1020,7 +1002,6 @@ __global__ __launch_bounds__(64) MCBA_F2_OCCUPANCY void k_lsmr_fused2(Dims d, Ta
     if (v < 0) continue;
     PF_STAMP(pf_a);
     const int b = v % d.B, c = (v / d.B) % d.C, f = d.f0 + v / (d.B * d.C);
-    constexpr int NPB64 = LIN_MAX_POINTS / 64;
     // the mask bytes of the first segment are requested in front of the parameter staging: one round trip for both
     uint8_t inb[NPB64];
     if constexpr (!DESC) {
@@ -1162,7 +1143,7 @@ __global__ __launch_bounds__(64) MCBA_F2_OCCUPANCY void k_lsmr_fused2(Dims d, Ta
         count += __popcll(m);
       }
       lds_fence();
-      // observation, board point and old uhat of the NEXT chunk are requested before the current one is evaluated (as in k_cost)
+      // observation, board point and old uhat of the NEXT chunk are requested before the current one is evaluated (first_chunk, in this kernel's own words)
       int p_cur = lane < count ? pidx[lane] : 0;
       ob_cur = t.obs[(size_t)v * d.P + p_cur];
       double X_cur[3], X_nxt[3];
@@ -1345,9 +1326,9 @@ __global__ void k_jacobian(Dims d, Tables t, int row_nnz, double* __restrict__ v
 template <int ND, int FISH, int MOTION, bool OPTK>
 __global__ __launch_bounds__(256) void k_points(Dims d, Tables t, double* __restrict__ Hss, double* __restrict__ Hfs,
                                                 double* __restrict__ g) {
-  constexpr bool ROLL = MOTION == MOTION_ROLLING;
-  constexpr int DE = ROLL ? 12 : 6, NPB = MOTION == MOTION_STATIC ? 3 : 4, KI = OPTK ? 4 + ND : 0;
-  constexpr int NV = DE + KI + 1, NPC = 6 * NPB, CW = 6 + KI;
+  using VS = ViewShape<ND, MOTION, OPTK>;
+  constexpr bool ROLL = VS::ROLL;
+  constexpr int DE = VS::DE, NPB = VS::NPB, KI = VS::KI, NV = VS::NV, NPC = VS::NPC, CW = 6 + KI;
   constexpr int NMISC = 18 + 6 + 3 + (MOTION == MOTION_HAND_EYE ? 36 : 0);   // board | pt-pt | g | hand-eye
   __shared__ double red[4][3 * CW > NMISC ? 3 * CW : NMISC];
 
@@ -1507,15 +1488,15 @@ void k_linearize(Dims d, Tables t, double* __restrict__ rec,
   constexpr bool FUSED = FUSED_MODE != 0;
   constexpr bool COMPACT = FUSED_MODE == 3;
   (void)x; (void)cp;
-  constexpr bool ROLL = MOTION == MOTION_ROLLING;
-  constexpr int DE = ROLL ? 12 : 6, NPB = MOTION == MOTION_STATIC ? 3 : 4, KI = OPTK ? 4 + ND : 0;
-  constexpr int NV = DE + KI + 1, NT = (NV + 15) / 16, NVP = 16 * NT;
+  using VS = ViewShape<ND, MOTION, OPTK>;
+  constexpr bool ROLL = VS::ROLL;
+  constexpr int DE = VS::DE, NPB = VS::NPB, NPC = VS::NPC, KI = VS::KI, NV = VS::NV, NT = (NV + 15) / 16, NVP = 16 * NT;
   // shifted-tile kernels (see TAILV below) never read a column >= NV: their staging rows and their epilogue copy of S are
   // NV wide instead of 32 (LDS per workgroup 20.4 -> 16.1 KB at NV = 22)
   constexpr bool NARROW = MFMA && NT == 2 && NV - 16 <= 7;
   constexpr int LDV = (NARROW ? NV : NVP) + 1;
   constexpr int SLD = NARROW ? ((NV + 1) & ~1) : NVP, SROWS = NARROW ? NV : NVP;   // epilogue S: SROWS x SLD
-  constexpr int NPC = 6 * NPB, NL = NPC + KI, N1 = NL + 1;
+  constexpr int NL = NPC + KI, N1 = NL + 1;
   // staging: one LDS row per lane; a chunk of 64 observations is accumulated in TWO rounds, first the u-rows of all 64
   // lanes, then the v-rows (S = sum of the outer products of all rows: the order is free).  Compared with staging the
   // row pairs of 32 lanes per round this issues half as many ds_write instructions (every lane is active in every store)
@@ -1571,7 +1552,6 @@ void k_linearize(Dims d, Tables t, double* __restrict__ rec,
   // (a dynamic hand-out of the views through an atomic counter was measured slower at every size: static stride it is)
   const int n_active = t.active_views[0];
   (void)epoch;   // (de-phasing the workgroups with a start-up delay per blockIdx & 3 was measured: only slower)
-  constexpr int NPB64 = LIN_MAX_POINTS / 64;
   constexpr int NTL = (DE * NPC + 63) / 64;
   // ---- front of a view: registers filled by front_issue, consumed by front_finish -----------------------------------
   uint8_t inb[NPB64];

@@ -52,9 +52,9 @@ __global__ __launch_bounds__(64) void k_obscov(Dims d, Tables t, const double* _
                                                const double* __restrict__ Sfs, const uint8_t* __restrict__ pflag, double sigma2,
                                                double* __restrict__ pred_cov, double* __restrict__ student,
                                                double* __restrict__ vpart, const double* __restrict__ gview) {
-  constexpr bool ROLL = MOTION == MOTION_ROLLING;
-  constexpr int DE = ROLL ? 12 : 6, NPB = MOTION == MOTION_STATIC ? 3 : 4, NPC = 6 * NPB, KI = OPTK ? 4 + ND : 0;
-  constexpr int NL = NPC + KI, NG = DE + KI, NV = NG + 1;
+  using VS = ViewShape<ND, MOTION, OPTK>;
+  constexpr bool ROLL = VS::ROLL;
+  constexpr int DE = VS::DE, NPC = VS::NPC, KI = VS::KI, NL = NPC + KI, NG = VS::NS, NV = VS::NV;
   constexpr int NE = (NL * NL + 63) / 64;
   static_assert(NL <= 64, "one lane per local parameter");
   __shared__ int code[NL], flagged[NL];
@@ -153,9 +153,8 @@ __global__ __launch_bounds__(64) void k_obscov(Dims d, Tables t, const double* _
     // ---- per point ----
     double tr_acc = 0.0, mx = 0.0;
     // The slots to predict (valid or inlier: ~30 % of a real rig's table) are ballot-compacted into a point list per segment of
-    // LIN_MAX_POINTS slots, as k_lsmr_jv compacts its inliers, and the forms below run on dense 64-lane chunks; the other slots
+    // LIN_MAX_POINTS slots, as inlier_list (mcba_kernels.h) compacts the inliers, and the forms below run on dense 64-lane chunks; the other slots
     // of the segment get their zeros on the way.
-    constexpr int NPB64 = LIN_MAX_POINTS / 64;
     for (int seg0 = 0; seg0 < d.P; seg0 += LIN_MAX_POINTS) {
     int count = 0;
 #pragma unroll
