@@ -406,6 +406,43 @@ int32_t mcba_view_poses(const mcba_view_pose_problem* p, double* poses, double* 
  * [1] uploads, [2] kernel, [3] downloads + scatter; *n_active (or NULL) = views launched                               */
 int32_t mcba_debug_view_poses_ms(double* ms /*[4]*/, int64_t* n_active);
 
+/* --- single-camera intrinsic calibration: Camera.calibrate / CameraFisheye.calibrate (camera.py:69-105) ------------ */
+/* Intrinsics of every camera from its own detections, all cameras in one call (csrc/mcba_intrinsic.h: homography + focal start,
+ * per-view poses by the mathematics of mcba_view_poses, then Levenberg-Marquardt over fx fy cx cy | dist | one pose per view with
+ * the views eliminated by a Schur complement, iterated to convergence).  A view is one (frame, board) slot.  Handle-less like
+ * mcba_view_poses; same error convention, the caller owns every array.                                                     */
+#define MCBA_CAMERA_OK 0             /* the converged optimum                                                            */
+#define MCBA_CAMERA_TOO_FEW_VIEWS 1  /* fewer than 3 usable views                                                        */
+#define MCBA_CAMERA_DEGENERATE 2     /* no focal start (e.g. every view fronto-parallel) or a non-finite cost            */
+#define MCBA_CAMERA_NOT_CONVERGED 3  /* the step test was not met within max_iterations (the last iterate is returned)   */
+#define MCBA_CAMERA_MASKED 4         /* every view of the camera is masked out                                           */
+typedef struct mcba_intrinsic_problem {
+  int32_t C, F, B, P;             /* cameras, frames, boards, padded corners per board                                 */
+  const double* points;           /* [C,F,B,P,2] detected corners (pixels)                                             */
+  const uint8_t* valid;           /* [C,F,B,P]                                                                         */
+  const double* board_points;     /* [B,P,3] board geometry, padded                                                    */
+  const int32_t* board_sizes;     /* [B] corners of every board, or NULL = P                                           */
+  const double* image_sizes;      /* [C,2] width, height                                                               */
+  int32_t n_dist;                 /* width of the dist part of every camera block (4 .. 14)                            */
+  const int32_t* camera_n_dist;   /* [C] coefficients each camera really has (4, 5, 8, 12 or 14), or NULL = n_dist      */
+  const uint8_t* is_fisheye;      /* [C] Kannala-Brandt (4 coefficients), or NULL = none                                */
+  const uint8_t* fix_aspect;      /* [C] fy = fx, or NULL = none                                                        */
+  const uint8_t* free_dist;       /* [C,n_dist] 1 = estimated, 0 = held at its start value; NULL = all of the camera's  */
+  const uint8_t* view_mask;       /* [C,F,B] views to use, or NULL = every view; views under 4 corners are never used   */
+  const double* init_cameras;     /* [C, 5 + n_dist] warm start, or NULL = the homography start                         */
+  const double* init_poses;       /* [C,F,B,4,4] warm start (given exactly when init_cameras is)                        */
+  int32_t max_iterations;         /* Levenberg-Marquardt passes per camera; <= 0: 100                                   */
+  int32_t* lm_iterations;         /* OUT [C] passes used, or NULL                                                       */
+} mcba_intrinsic_problem;
+/* cameras [C, 5 + n_dist] blocks [fx fy cx cy skew dist...] (skew 0; under fix_aspect fy = fx); poses [C,F,B,4,4] board ->
+ * camera; sse [C,F,B] sum of squared pixel distances of the view at the optimum; n_used [C,F,B]; view_status MCBA_VIEW_*;
+ * camera_status [C] MCBA_CAMERA_*.  Views that are not used: identity, sse 0, n_used 0.                                  */
+int32_t mcba_calibrate_intrinsics(const mcba_intrinsic_problem* p, double* cameras, double* poses, double* sse, int32_t* n_used,
+                                  uint8_t* view_status, uint8_t* camera_status);
+/* timing of the last mcba_calibrate_intrinsics call of this thread, milliseconds: [0] host preparation + compaction, [1] uploads,
+ * [2] kernels (start, view poses, refinement), [3] downloads + scatter; *n_views (or NULL) = views uploaded             */
+int32_t mcba_debug_calibrate_intrinsics_ms(double* ms /*[4]*/, int64_t* n_views);
+
 /* --- solve -------------------------------------------------------------------------------------------------- */
 /* Trust-region least squares: replaces scipy.optimize.least_squares(method='trf', x_scale='jac', jac_sparsity=S,
  * loss, f_scale, ftol, max_nfev) at calibration.py:209-210.  x is updated in place to `res.x`.                 */

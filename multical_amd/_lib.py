@@ -63,6 +63,14 @@ class ViewPoseProblem(C.Structure):   # mcba_view_pose_problem
               ("max_iterations", C.c_int32), ("lm_iterations", c_int32_p)]
 
 
+class IntrinsicProblem(C.Structure):   # mcba_intrinsic_problem
+  _fields_ = [("C", C.c_int32), ("F", C.c_int32), ("B", C.c_int32), ("P", C.c_int32),
+              ("points", c_double_p), ("valid", c_uint8_p), ("board_points", c_double_p), ("board_sizes", c_int32_p),
+              ("image_sizes", c_double_p), ("n_dist", C.c_int32), ("camera_n_dist", c_int32_p), ("is_fisheye", c_uint8_p),
+              ("fix_aspect", c_uint8_p), ("free_dist", c_uint8_p), ("view_mask", c_uint8_p), ("init_cameras", c_double_p),
+              ("init_poses", c_double_p), ("max_iterations", C.c_int32), ("lm_iterations", c_int32_p)]
+
+
 LOG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p)
 
@@ -95,6 +103,9 @@ SYMBOLS = [
                                            c_int32_p, c_uint8_p, C.c_double, C.c_int32, c_double_p, c_uint8_p, c_uint8_p]),
   ("mcba_view_poses", C.c_int32, [C.POINTER(ViewPoseProblem), c_double_p, c_double_p, c_int32_p, c_uint8_p]),
   ("mcba_debug_view_poses_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_calibrate_intrinsics", C.c_int32, [C.POINTER(IntrinsicProblem), c_double_p, c_double_p, c_double_p, c_int32_p, c_uint8_p,
+                                            c_uint8_p]),
+  ("mcba_debug_calibrate_intrinsics_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_error_stats", C.c_int32, [H, c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), c_double_p,
                                    C.POINTER(C.c_int64), c_double_p]),
   ("mcba_error_count", C.c_int32, [H, C.c_int32, C.POINTER(C.c_int64)]),

@@ -2,7 +2,8 @@
 
 Only the bundle-adjustment face of the reference classes is mirrored: intrinsic matrix + distortion <-> parameter
 vector [fx fy | cx cy | skew | dist].  `project` lives in the HIP kernels (csrc/mcba_math.h: project_point) -- there is
-no OpenCV in this package.  Intrinsic calibration (cv2.calibrateCamera*) is upstream of the hot path and out of scope.
+no OpenCV in this package.  Intrinsic calibration (Camera.calibrate, CameraFisheye.calibrate, calibrate_cameras: camera.py:69-105,
+229-241, camera_fisheye.py:71-94) runs on the device: tables.calibrate_intrinsics solves all cameras of a round in one call.
 """
 from functools import cached_property
 import numpy as np
@@ -15,9 +16,12 @@ DIST_SIZES = dict(standard=(4, 5), rational=(8,), thin_prism=(12,), tilted=(14,)
 class Camera(Parameters):
   model_names = ("standard", "rational", "tilted", "thin_prism")
 
-  def __init__(self, image_size, intrinsic, dist, model='standard', fix_aspect=False, has_skew=False):
+  def __init__(self, image_size, intrinsic, dist, model='standard', fix_aspect=False, has_skew=False, error_perview=None,
+               intrinsic_dataset=None):
     assert model in self.model_names, f"unknown camera model {model} options are {list(self.model_names)}"
     self.model = model
+    self.error_perview = error_perview                                               # (optional: outside __getstate__,
+    self.intrinsic_dataset = {} if intrinsic_dataset is None else intrinsic_dataset  #  as in the reference)
     self.image_size = tuple(image_size)
     self.intrinsic = np.asarray(intrinsic, dtype=np.float64)
     self.dist = np.zeros(5) if dist is None else np.asarray(dist, dtype=np.float64)
@@ -69,6 +73,14 @@ class Camera(Parameters):
     d.update(k)
     return self.__class__(**d)
 
+  @staticmethod
+  def calibrate(boards, intrinsic_error_limit, detections, image_size, max_iter=10, eps=1e-3, model='standard', fix_aspect=False,
+                has_skew=False, flags=0, max_images=None):
+    """camera.py:69-105 for one camera: (camera, err).  See calibrate_cameras for what differs from the reference."""
+    cams, errs = calibrate_cameras(boards, [detections], [image_size], intrinsic_error_limit, max_iter=max_iter, eps=eps,
+                                   model=model, fix_aspect=fix_aspect, has_skew=has_skew, flags=flags, max_images=max_images)
+    return cams[0], errs[0]
+
   def __repr__(self):
     return f"{type(self).__name__}(image_size={self.image_size}, intrinsic={self.intrinsic.tolist()}, dist={self.dist.tolist()})"
 
@@ -76,3 +88,174 @@ class Camera(Parameters):
 class CameraFisheye(Camera):
   """Kannala-Brandt fisheye (camera_fisheye.py:28): same parameter block, cv2.fisheye.projectPoints forward model."""
   model_names = ("standard", "fix_k1", "fix_k2", "fix_k3", "fix_k4")
+
+  @staticmethod
+  def calibrate(boards, detections, image_size, max_iter=10, eps=1e-3, model='standard', fix_aspect=False, has_skew=False, flags=0,
+                max_images=None):
+    """camera_fisheye.py:71-94 for one camera: (camera, err).  See calibrate_cameras_fisheye."""
+    cams, errs = calibrate_cameras_fisheye(boards, [detections], [image_size], max_iter=max_iter, eps=eps, model=model,
+                                           fix_aspect=fix_aspect, has_skew=has_skew, flags=flags, max_images=max_images)
+    return cams[0], errs[0]
+
+
+# ---- intrinsic calibration from detections (camera.py:184-241) ---------------------------------------------------------------
+# detections: per frame a list with one struct(ids, corners) per board, as the reference's detect step returns them
+def _has_min_detections(board, detection):
+  if hasattr(board, "has_min_detections"):
+    return board.has_min_detections(detection)
+  from . import tables
+  ids = np.asarray(detection.ids, dtype=np.int64).ravel()
+  n = int(getattr(board, "num_points", len(np.asarray(board.points))))
+  valid = np.zeros((1, 1, 1, n), dtype=bool)
+  valid[0, 0, 0, ids] = True
+  return len(ids) >= 4 and bool(tables.min_detections_mask(valid, [board])[0, 0, 0])
+
+
+def board_correspondences(board_id, board, detections):
+  """The views of one board (camera.py:184-195): detections = that board's struct(ids, corners) of every frame."""
+  kept = [(i, d) for i, d in enumerate(detections) if _has_min_detections(board, d)]
+  pts = np.asarray(board.points)
+  return struct(corners=[np.asarray(d.corners, dtype=np.float32).reshape(-1, 2) for _, d in kept],
+                ids=[np.asarray(d.ids).ravel() for _, d in kept],
+                object_points=[pts[np.asarray(d.ids).ravel()].astype(np.float32) for _, d in kept],
+                board_offset=[float(board_id)] * len(kept), image_ids=[i for i, _ in kept])
+
+
+def calibration_points(boards, detections):
+  """All views of one camera, board by board (camera.py:229-235): struct of parallel lists corners, ids, object_points,
+  board_offset, image_ids."""
+  per_board = [board_correspondences(b, board, [frame[b] for frame in detections]) for b, board in enumerate(boards)]
+  return struct(**{k: [x for pb in per_board for x in pb[k]] for k in ("corners", "ids", "object_points", "board_offset", "image_ids")})
+
+
+def coverage(corners, bins):
+  """Number of image bins that hold a corner (camera.py:206-210)."""
+  corners = np.asarray(corners).reshape(-1, 2)
+  hist, _, _ = np.histogram2d(corners[:, 0], corners[:, 1], bins)
+  return int(np.count_nonzero(hist))
+
+
+def image_bins(image_size, approx_bins=10):
+  bin_size = min(image_size[0] / approx_bins, image_size[1] / approx_bins)
+  return [np.linspace(0, image_size[axis], int(image_size[axis] / bin_size)) for axis in (0, 1)]
+
+
+def top_detection_coverage(detections, k, image_size, approx_bins=10, jitter=0.1, rng=None):
+  """The k views that cover the most image bins (camera.py:219-227).
+
+  DEVIATION from the reference: it adds np.random.normal(0, jitter * approx_bins**2) -- a standard deviation of 10 bins, unseeded --
+  to every view's bin count before sorting, so its choice differs from run to run.  Here rng=None means NO jitter and a stable
+  order (ties keep their order in the list); passing a numpy Generator draws the reference's jitter from it."""
+  bins = image_bins(image_size, approx_bins=10)
+  sizes = np.array([-float(coverage(c, bins)) for c in detections.corners])
+  if rng is not None:
+    sizes = sizes + rng.normal(0, jitter * (approx_bins * approx_bins), len(sizes))
+  order = np.argsort(sizes, kind='stable')[:k]
+  return detections._map(lambda xs: [xs[i] for i in order])
+
+
+def _solve(*args, **kwargs):
+  """The device call of a round (tables.calibrate_intrinsics); the tests of the rejection loop replace it."""
+  from . import tables
+  return tables.calibrate_intrinsics(*args, **kwargs)
+
+
+def _dense_views(boards, points_per_camera, n_frames):
+  """Detection table [C,F,B,P] of the listed views and the mask [C,F,B] of the slots they fill.  F is the number of frames of the
+  detections in every round, whatever views are left: the warm start of a round is the pose table of the round before."""
+  from .structs import Table
+  C_, B, F = len(points_per_camera), len(boards), int(n_frames)
+  P = max(len(np.asarray(b.points)) for b in boards)
+  pts, valid, mask = np.zeros((C_, F, B, P, 2)), np.zeros((C_, F, B, P), dtype=bool), np.zeros((C_, F, B), dtype=bool)
+  for c, p in enumerate(points_per_camera):
+    for corners, ids, b, f in zip(p.corners, p.ids, p.board_offset, p.image_ids):
+      pts[c, f, int(b), ids] = corners
+      valid[c, f, int(b), ids] = True
+      mask[c, f, int(b)] = True
+  return Table.create(points=pts, valid=valid), mask
+
+
+def _solved_views(res, c, points):
+  """The views of camera c that entered the solution: a view without a start pose (collinear corners: VIEW_DEGENERATE) has no
+  error and no pose, so it leaves the list -- it is neither counted in the quantile nor warm-started at the identity."""
+  from . import tables
+  keep = [i for i, (b, f) in enumerate(zip(points.board_offset, points.image_ids)) if res.view_status[c, f, int(b)] == tables.VIEW_OK]
+  return points if len(keep) == len(points.image_ids) else points._map(lambda xs: [xs[i] for i in keep])
+
+
+def _require_result(res, c):
+  from . import tables
+  if res.camera_status[c] not in (tables.CAMERA_OK, tables.CAMERA_NOT_CONVERGED):
+    names = {tables.CAMERA_TOO_FEW_VIEWS: "fewer than 3 usable views", tables.CAMERA_DEGENERATE: "degenerate views (no focal start)",
+             tables.CAMERA_MASKED: "no views"}
+    raise RuntimeError(f"intrinsic calibration of camera {c} failed: {names.get(int(res.camera_status[c]), res.camera_status[c])}")
+
+
+def _camera_of(res, c, cls, image_size, model, fix_aspect, has_skew, points):
+  blk, nd = res.cameras[c], int(res.camera_n_dist[c])
+  K = np.array([[blk[0], 0.0, blk[2]], [0.0, blk[1], blk[3]], [0.0, 0.0, 1.0]])
+  per_view = np.array([res.error_perview[c, f, int(b)] for b, f in zip(points.board_offset, points.image_ids)])
+  return cls(image_size=image_size, intrinsic=K, dist=blk[5:5 + nd].copy(), model=model, fix_aspect=fix_aspect, has_skew=has_skew,
+             error_perview=per_view, intrinsic_dataset={'board_ids': list(points.board_offset), 'image_ids': list(points.image_ids)})
+
+
+def calibrate_cameras(boards, points, image_sizes, intrinsic_error_limit, max_iter=10, eps=1e-3, model='standard', fix_aspect=False,
+                      has_skew=False, flags=0, max_images=None):
+  """camera.py:237-241 + the loop of Camera.calibrate (camera.py:84-99): (cameras, errs).  points: the detections of every camera.
+
+  A round solves ALL cameras that are not finished in one device call (tables.calibrate_intrinsics); err = sqrt(sum sse / sum n),
+  per-view error = sqrt(sse_v / n_v).  While |err| >= its limit a camera with 15 views or more rounds err to two decimals and
+  keeps the views below the 0.95 quantile of the per-view errors; one with fewer raises its limit by 0.1.  Differences from the
+  reference: a view whose corners give no start pose (collinear) leaves the list; finished cameras are masked out of later rounds; a round starts from the previous solution; the reference's repeat
+  solve on unchanged data (fewer than 15 views) is skipped -- its result is the same.  max_iter, eps and flags are accepted and
+  UNUSED: the solve goes to the optimum of the reprojection cost, not to cv2's (max_iter, eps) stop.  Skew is not estimated."""
+  assert model in Camera.model_names, f"unknown camera model {model} options are {list(Camera.model_names)}"
+  n = len(points)
+  n_frames = max(len(d) for d in points)
+  views = [calibration_points(boards, d) for d in points]
+  if max_images is not None:
+    views = [top_detection_coverage(v, max_images, size) for v, size in zip(views, image_sizes)]
+  limits, errs = [float(intrinsic_error_limit)] * n, [float(intrinsic_error_limit)] * n
+  cameras, init = [None] * n, None
+  active = [c for c in range(n) if abs(errs[c]) >= limits[c]]
+  while active:
+    table, mask = _dense_views(boards, views, n_frames)
+    mask[[c for c in range(n) if c not in active]] = False
+    res = _solve(table, boards, image_sizes, model=model, fix_aspect=fix_aspect, view_mask=mask, init=init)
+    init = (res.cameras, res.poses)
+    for c in active:
+      _require_result(res, c)
+      v = views[c] = _solved_views(res, c, views[c])
+      cameras[c] = _camera_of(res, c, Camera, image_sizes[c], model, fix_aspect, has_skew, v)
+      per_view, errs[c] = cameras[c].error_perview, float(res.error[c])
+      if len(per_view) >= 15:
+        errs[c] = float("{:.2f}".format(errs[c]))
+        threshold = np.quantile(per_view, 0.95)
+        keep = [i for i, e in enumerate(per_view) if e < threshold]
+        views[c] = v._map(lambda xs: [xs[i] for i in keep])
+        cameras[c].intrinsic_dataset = {'board_ids': list(views[c].board_offset), 'image_ids': list(views[c].image_ids)}
+      else:
+        while abs(errs[c]) >= limits[c]:     # (the reference solves the same views again after every step of the limit)
+          limits[c] += 0.1
+    active = [c for c in active if abs(errs[c]) >= limits[c]]
+  return cameras, errs
+
+
+def calibrate_cameras_fisheye(boards, points, image_sizes, max_iter=10, eps=1e-3, model='standard', fix_aspect=False, has_skew=False,
+                              flags=0, max_images=None):
+  """camera_fisheye.py:71-94 for every camera, all of them in ONE device call: (cameras, errs).  One solve over every view that
+  passes has_min_detections, no rejection rounds (the reference has none for fisheye cameras).  `fix_kN` holds that coefficient at
+  0 (cv2.fisheye.CALIB_FIX_KN); skew is never estimated (the reference passes CALIB_FIX_SKEW).  max_iter, eps and flags are
+  accepted and unused: the solution is the optimum of the reprojection cost."""
+  assert model in CameraFisheye.model_names, f"unknown camera model {model} options are {list(CameraFisheye.model_names)}"
+  views = [calibration_points(boards, d) for d in points]
+  if max_images is not None:
+    views = [top_detection_coverage(v, max_images, size) for v, size in zip(views, image_sizes)]
+  free = [0 if model == f"fix_k{i + 1}" else 1 for i in range(4)]
+  table, mask = _dense_views(boards, views, max(len(d) for d in points))
+  res = _solve(table, boards, image_sizes, model='fisheye', fix_aspect=fix_aspect, view_mask=mask, free_dist=[free] * len(views))
+  cameras = []
+  for c, v in enumerate(views):
+    _require_result(res, c)
+    cameras.append(_camera_of(res, c, CameraFisheye, image_sizes[c], model, fix_aspect, has_skew, _solved_views(res, c, v)))
+  return cameras, [float(e) for e in res.error]

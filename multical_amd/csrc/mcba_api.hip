@@ -38,6 +38,8 @@
 #include "mcba_init_kernels.h"
 #include "mcba_pnp_kernels.h"
 #include "mcba_pnp_driver.h"
+#include "mcba_intrinsic_kernels.h"
+#include "mcba_intrinsic_driver.h"
 
 using namespace mcba;
 
@@ -2063,6 +2065,182 @@ int32_t mcba_debug_view_poses_ms(double* ms, int64_t* n_active) {
   REQUIRE(ms, "null argument");
   for (int i = 0; i < 4; ++i) ms[i] = g_view_pose_ms[i];
   if (n_active) *n_active = g_view_pose_active;
+  API_END
+}
+
+// ---- intrinsic calibration (csrc/mcba_intrinsic.h, k_calibrate_camera) ---------------------------------------------------
+namespace {
+thread_local double g_intrinsic_ms[4] = {0.0, 0.0, 0.0, 0.0};
+thread_local int64_t g_intrinsic_views = 0;
+
+void calibrate_intrinsics(const mcba_intrinsic_problem& p, double* cameras, double* poses, double* sse, int32_t* n_used,
+                          uint8_t* view_status, uint8_t* camera_status) {
+  const double t0 = now_seconds();
+  intr::IntrinsicPlan plan;
+  std::string err;
+  if (!intr::plan_intrinsics(p, plan, err)) throw Error(err);
+  REQUIRE(pnp::view_pose_npl(p.P) > 0, "mcba_calibrate_intrinsics: boards of more than 1024 corners are not served");
+  intr::fill_unsolved(p, plan, cameras, poses, sse, n_used, view_status, camera_status);
+  const size_t na = plan.active.size(), P = (size_t)p.P, nc = (size_t)p.C;
+  g_intrinsic_views = (int64_t)na;
+  for (double& v : g_intrinsic_ms) v = 0.0;
+  if (na == 0) {                       // no camera to solve: nothing is uploaded or launched, the device is not touched
+    g_intrinsic_ms[0] = (now_seconds() - t0) * 1e3;
+    return;
+  }
+  hipStream_t st = resource_cache().take_stream();
+  if (st == nullptr) HIP_OK(hipStreamCreate(&st));
+  struct StreamGuard {
+    hipStream_t s;
+    ~StreamGuard() {
+      if (!resource_cache().park_stream(s)) (void)hipStreamDestroy(s);
+    }
+  } guard{st};
+  g_fill_stream = st;
+  struct ParkReset { ~ParkReset() { g_park_on_release = false; } } park_reset;   // (declared first: runs after the buffers went)
+  // the rows of the views of the cameras that are solved, gathered into pinned memory (camera-major: a camera's views are one run)
+  const size_t px_bytes = na * P * 2 * sizeof(double), ok_bytes = na * P, in_bytes = plan.warm ? na * 16 * sizeof(double) : 0;
+  const size_t stage_bytes = px_bytes + in_bytes + ok_bytes;
+  char* stage = (char*)pinned_alloc(stage_bytes);
+  struct PinGuard { void* q; size_t n; ~PinGuard() { pinned_free(q, n); } } pin_guard{stage, stage_bytes};
+  double* h_px = (double*)stage;
+  double* h_in = (double*)(stage + px_bytes);
+  uint8_t* h_ok = (uint8_t*)(stage + px_bytes + in_bytes);
+  for (size_t k = 0; k < na; ++k) {
+    const size_t v = (size_t)plan.active[k];
+    memcpy(h_px + k * P * 2, p.points + v * P * 2, P * 2 * sizeof(double));
+    memcpy(h_ok + k * P, p.valid + v * P, P);
+    if (plan.warm) memcpy(h_in + k * 16, p.init_poses + v * 16, 16 * sizeof(double));
+  }
+  std::vector<double> h_blk(nc * intr::BLK, 0.0);
+  if (plan.warm)
+    for (size_t c = 0; c < nc; ++c)
+      for (int i = 0; i < 5 + p.n_dist; ++i) h_blk[c * intr::BLK + i] = p.init_cameras[c * (5 + (size_t)p.n_dist) + i];
+  std::vector<int32_t> h_group;
+  for (const auto& g : plan.group_cameras) h_group.insert(h_group.end(), g.begin(), g.end());
+  DevBuf<double> d_px, d_pose, d_board, d_planes, d_mask, d_size, d_hv, d_blk, d_entry, d_sse, d_ws;
+  DevBuf<uint8_t> d_ok, d_fa, d_fish, d_vstatus, d_cstatus;
+  DevBuf<int32_t> d_desc, d_first, d_nd, d_int, d_group;
+  d_px.alloc(na * P * 2, false);
+  d_ok.alloc(na * P, false);
+  d_pose.alloc(na * 16, false);
+  d_board.alloc((size_t)p.B * P * 3, false);
+  d_planes.alloc(plan.planes.size(), false);
+  d_mask.alloc(plan.mask.size(), false);
+  d_size.alloc(2 * nc, false);
+  d_hv.alloc(na * 10, false);
+  d_blk.alloc(nc * intr::BLK, false);
+  d_entry.alloc(nc * CAM_STRIDE, false);
+  d_sse.alloc(na, false);
+  d_ws.alloc(na * intr::VB_STRIDE, false);
+  d_fa.alloc(nc, false);
+  d_fish.alloc(nc, false);
+  d_vstatus.alloc(na, false);
+  d_cstatus.alloc(nc, false);
+  d_desc.alloc(2 * na, false);
+  d_first.alloc(nc + 1, false);
+  d_nd.alloc(nc, false);
+  d_int.alloc(3 * na + nc, false);       // n_used [na] | iterations of the start poses [na] | usable views [na] | LM passes [C]
+  d_group.alloc(h_group.size(), false);
+  const double t1 = now_seconds();
+  HIP_OK(hipMemcpyAsync(d_px.p, h_px, px_bytes, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_ok.p, h_ok, ok_bytes, hipMemcpyHostToDevice, st));
+  if (plan.warm) HIP_OK(hipMemcpyAsync(d_pose.p, h_in, in_bytes, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_board.p, p.board_points, (size_t)p.B * P * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_planes.p, plan.planes.data(), plan.planes.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_mask.p, plan.mask.data(), plan.mask.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_size.p, plan.image_size.data(), 2 * nc * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_blk.p, h_blk.data(), h_blk.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_fa.p, plan.cam_fa.data(), nc, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_fish.p, plan.cam_fish.data(), nc, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_cstatus.p, plan.cam_status.data(), nc, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_desc.p, plan.desc.data(), 2 * na * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_first.p, plan.cam_first.data(), (nc + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_nd.p, plan.cam_nd.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_group.p, h_group.data(), h_group.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemsetAsync(d_vstatus.p, 0, na, st));                       // (warm start: every view is usable)
+  HIP_OK(hipMemsetAsync(d_int.p, 0, (3 * na + nc) * sizeof(int32_t), st));
+  HIP_OK(hipStreamSynchronize(st));
+  const double t2 = now_seconds();
+  intr::IntrinsicArgs a;
+  a.P = p.P; a.max_iter = plan.max_iter; a.warm = plan.warm ? 1 : 0;
+  a.pixel = d_px.p; a.valid = d_ok.p; a.desc = d_desc.p; a.board = d_board.p; a.planes = d_planes.p; a.cam_first = d_first.p;
+  a.cam_fa = d_fa.p; a.cam_fish = d_fish.p; a.cam_nd = d_nd.p; a.mask = d_mask.p; a.image_size = d_size.p; a.Hv = d_hv.p;
+  a.blk = d_blk.p; a.cam_entry = d_entry.p; a.pose = d_pose.p; a.vstatus = d_vstatus.p; a.sse = d_sse.p; a.n_used = d_int.p;
+  a.ws = d_ws.p; a.ulist = d_int.p + 2 * na; a.cam_iters = d_int.p + 3 * na; a.cam_status = d_cstatus.p; a.group = d_group.p;
+  if (!plan.warm) {
+    // homographies and the focal start, then the start pose of every view with that camera: k_view_pose on the resident rows
+    HIP_OK(intr::intrinsic_start_launch(a, (int)na, p.C, st));
+    pnp::ViewPoseArgs vp;
+    vp.n_active = (int)na; vp.P = p.P; vp.max_iter = 50;
+    vp.pixel = d_px.p; vp.valid = d_ok.p; vp.desc = d_desc.p; vp.init = nullptr; vp.board = d_board.p;
+    vp.cam = d_entry.p; vp.cam_nd = d_nd.p; vp.cam_fish = d_fish.p; vp.planes = d_planes.p;
+    vp.pose = d_pose.p; vp.sse = d_sse.p; vp.n_used = d_int.p; vp.iters = d_int.p + na; vp.status = d_vstatus.p;
+    pnp::view_pose_launch(vp, st);
+    check_launch("k_view_pose (intrinsic start)");
+  }
+  size_t g0 = 0;
+  for (size_t g = 0; g < plan.groups.size(); ++g) {   // one launch per camera family: a rig may mix them
+    a.group = d_group.p + g0;
+    HIP_OK(intr::calibrate_camera_launch(a, plan.groups[g].first, plan.groups[g].second != 0, (int)plan.group_cameras[g].size(), st));
+    g0 += plan.group_cameras[g].size();
+  }
+  HIP_OK(hipStreamSynchronize(st));
+  const double t3 = now_seconds();
+  std::vector<double> h_pose(na * 16), h_sse(na);
+  std::vector<int32_t> h_int(3 * na + nc);
+  std::vector<uint8_t> h_vstatus(na), h_cstatus(nc);
+  HIP_OK(hipMemcpyAsync(h_blk.data(), d_blk.p, h_blk.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(h_pose.data(), d_pose.p, na * 16 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(h_sse.data(), d_sse.p, na * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(h_int.data(), d_int.p, h_int.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(h_vstatus.data(), d_vstatus.p, na, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(h_cstatus.data(), d_cstatus.p, nc, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  for (int c = 0; c < p.C; ++c) {
+    if (plan.cam_first[c + 1] == plan.cam_first[c]) continue;   // (not solved: fill_unsolved has said so)
+    camera_status[c] = h_cstatus[c];
+    if (p.lm_iterations) p.lm_iterations[c] = h_int[3 * na + c];
+    if (!intr::camera_has_result(h_cstatus[c])) {
+      intr::drop_camera_views(plan, c, poses, sse, n_used, view_status);
+      continue;
+    }
+    for (int i = 0; i < 5 + plan.cam_nd[c]; ++i) cameras[(size_t)c * (5 + p.n_dist) + i] = h_blk[(size_t)c * intr::BLK + i];
+    for (int k = plan.cam_first[c]; k < plan.cam_first[c + 1]; ++k) {
+      const size_t v = (size_t)plan.active[k];
+      view_status[v] = h_vstatus[k];
+      if (h_vstatus[k] != (uint8_t)pnp::ST_OK) continue;
+      memcpy(poses + v * 16, h_pose.data() + (size_t)k * 16, 16 * sizeof(double));
+      sse[v] = h_sse[k];
+      n_used[v] = h_int[k];
+    }
+  }
+  const double t4 = now_seconds();
+  g_intrinsic_ms[0] = (t1 - t0) * 1e3;
+  g_intrinsic_ms[1] = (t2 - t1) * 1e3;
+  g_intrinsic_ms[2] = (t3 - t2) * 1e3;
+  g_intrinsic_ms[3] = (t4 - t3) * 1e3;
+  if (getenv("MCBA_TIMING"))
+    fprintf(stderr, "[calibrate_intrinsics] %lld views of %d cameras, %d corners a row: plan + gather %.2f ms, uploads (%.1f MB) %.2f ms, "
+            "kernels %.2f ms, downloads + scatter %.2f ms\n", (long long)na, p.C, p.P, g_intrinsic_ms[0], (double)stage_bytes / 1e6,
+            g_intrinsic_ms[1], g_intrinsic_ms[2], g_intrinsic_ms[3]);
+  g_park_on_release = true;   // regular end: the buffers of this scope are parked for the next call of the same shape
+}
+}  // namespace
+
+int32_t mcba_calibrate_intrinsics(const mcba_intrinsic_problem* p, double* cameras, double* poses, double* sse, int32_t* n_used,
+                                  uint8_t* view_status, uint8_t* camera_status) {
+  API_BEGIN
+  REQUIRE(p && cameras && poses && sse && n_used && view_status && camera_status, "null argument");
+  calibrate_intrinsics(*p, cameras, poses, sse, n_used, view_status, camera_status);
+  API_END
+}
+
+int32_t mcba_debug_calibrate_intrinsics_ms(double* ms, int64_t* n_views) {
+  API_BEGIN
+  REQUIRE(ms, "null argument");
+  for (int i = 0; i < 4; ++i) ms[i] = g_intrinsic_ms[i];
+  if (n_views) *n_views = g_intrinsic_views;
   API_END
 }
 

@@ -414,3 +414,127 @@ def make_pose_table(point_table, boards, cameras, exclude_bad_poses=True, pose_e
   if return_info:
     return table, struct(status=status, sse=sse, num_used=n_used, error=error, lm_iterations=iters, view_mask=view_mask)
   return table
+
+
+# ---- intrinsic calibration: every camera from its own detections (camera.py:69-105, camera_fisheye.py:71-94) ---------------
+CAMERA_OK, CAMERA_TOO_FEW_VIEWS, CAMERA_DEGENERATE, CAMERA_NOT_CONVERGED, CAMERA_MASKED = 0, 1, 2, 3, 4   # mcba.h: MCBA_CAMERA_*
+
+# model -> (distortion coefficients, fisheye, coefficients estimated by default).  The masks restate OpenCV's flag semantics FROM
+# KNOWLEDGE OF OPENCV, unverifiable without a cv2 binary: without CALIB_RATIONAL_MODEL k4 k5 k6 stay 0, CALIB_THIN_PRISM_MODEL adds
+# s1..s4 and CALIB_TILTED_MODEL adds tau_x tau_y, each on top of k1 k2 p1 p2 k3 only.
+INTRINSIC_MODELS = dict(
+  standard=(5, False, [1] * 5),
+  rational=(8, False, [1] * 8),
+  thin_prism=(12, False, [1] * 5 + [0] * 3 + [1] * 4),
+  tilted=(14, False, [1] * 5 + [0] * 7 + [1] * 2),
+  pin4=(4, False, [1] * 4),
+  fisheye=(4, True, [1] * 4),
+)
+
+
+def _per_camera(value, n):
+  return list(value) if isinstance(value, (list, tuple, np.ndarray)) else [value] * n
+
+
+class IntrinsicInputs(object):
+  """The arrays of one mcba_intrinsic_problem, kept alive next to the ctypes struct that points into them."""
+
+  def __init__(self, points, valid, board_points, image_sizes, model='standard', fix_aspect=False, view_mask=None, init=None,
+               free_dist=None, max_iterations=0):
+    self.points = _f64(points)
+    self.valid = np.ascontiguousarray(np.asarray(valid).astype(np.uint8))
+    self.shape = self.valid.shape[:3]
+    C_, F, B = self.shape
+    P = self.valid.shape[3]
+    assert self.points.shape == (C_, F, B, P, 2) and len(board_points) == B and len(image_sizes) == C_
+    self.board_sizes = np.ascontiguousarray(np.array([len(b) for b in board_points], dtype=np.int32))
+    self.board_points = np.zeros((B, P, 3))
+    for b, pts in enumerate(board_points):
+      self.board_points[b, :len(pts)] = np.asarray(pts, dtype=np.float64)
+    self.image_sizes = _f64(np.asarray(image_sizes, dtype=np.float64).reshape(C_, 2))
+    self.models = _per_camera(model, C_)
+    for m in self.models:
+      if m not in INTRINSIC_MODELS:
+        raise ValueError(f"camera model {m!r}: one of {sorted(INTRINSIC_MODELS)}")
+    nds = [INTRINSIC_MODELS[m][0] for m in self.models]
+    self.n_dist = max(nds)
+    self.camera_n_dist = np.ascontiguousarray(np.array(nds, dtype=np.int32))
+    self.is_fisheye = np.ascontiguousarray(np.array([INTRINSIC_MODELS[m][1] for m in self.models], dtype=np.uint8))
+    self.fix_aspect = np.ascontiguousarray(np.array(_per_camera(fix_aspect, C_), dtype=np.uint8))
+    self.free_dist = np.zeros((C_, self.n_dist), dtype=np.uint8)
+    for c, m in enumerate(self.models):
+      self.free_dist[c, :nds[c]] = INTRINSIC_MODELS[m][2]
+    if free_dist is not None:
+      fd = np.asarray(free_dist).astype(np.uint8)
+      fd = np.broadcast_to(fd, (C_,) + fd.shape[-1:])
+      self.free_dist[:, :fd.shape[1]] = fd[:, :self.n_dist]
+      for c in range(C_):
+        self.free_dist[c, nds[c]:] = 0
+    self.view_mask = None if view_mask is None else np.ascontiguousarray(np.asarray(view_mask).astype(np.uint8))
+    assert self.view_mask is None or self.view_mask.shape == self.shape
+    self.init_cameras = self.init_poses = None
+    if init is not None:
+      cams, poses = init
+      self.init_cameras = np.zeros((C_, 5 + self.n_dist))
+      cams = np.asarray(cams, dtype=np.float64)
+      self.init_cameras[:, :cams.shape[1]] = cams[:, :5 + self.n_dist]
+      self.init_poses = _f64(poses)
+      assert self.init_poses.shape == self.shape + (4, 4)
+    self.max_iterations = int(max_iterations)
+    self.lm_iterations = np.zeros(C_, dtype=np.int32)
+
+  def struct(self):
+    dp, up, ip = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+    s = _lib.IntrinsicProblem()
+    s.C, s.F, s.B = self.shape
+    s.P = self.valid.shape[3]
+    s.points, s.valid = self.points.ctypes.data_as(dp), self.valid.ctypes.data_as(up)
+    s.board_points, s.board_sizes = self.board_points.ctypes.data_as(dp), self.board_sizes.ctypes.data_as(ip)
+    s.image_sizes, s.n_dist = self.image_sizes.ctypes.data_as(dp), self.n_dist
+    s.camera_n_dist, s.is_fisheye = self.camera_n_dist.ctypes.data_as(ip), self.is_fisheye.ctypes.data_as(up)
+    s.fix_aspect, s.free_dist = self.fix_aspect.ctypes.data_as(up), self.free_dist.ctypes.data_as(up)
+    s.view_mask = None if self.view_mask is None else self.view_mask.ctypes.data_as(up)
+    s.init_cameras = None if self.init_cameras is None else self.init_cameras.ctypes.data_as(dp)
+    s.init_poses = None if self.init_poses is None else self.init_poses.ctypes.data_as(dp)
+    s.max_iterations = self.max_iterations
+    s.lm_iterations = self.lm_iterations.ctypes.data_as(ip)
+    return s
+
+  def call(self, fn, *extra):
+    """fn(struct, cameras, poses, sse, n_used, view_status, camera_status, *extra) -> rc; returns (rc, result struct)."""
+    C_ = self.shape[0]
+    cameras, poses, sse = np.zeros((C_, 5 + self.n_dist)), np.empty(self.shape + (4, 4)), np.empty(self.shape)
+    n_used, vstat, cstat = np.empty(self.shape, dtype=np.int32), np.empty(self.shape, dtype=np.uint8), np.empty(C_, dtype=np.uint8)
+    dp, up, ip = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+    s = self.struct()
+    rc = fn(C.byref(s), cameras.ctypes.data_as(dp), poses.ctypes.data_as(dp), sse.ctypes.data_as(dp), n_used.ctypes.data_as(ip),
+            vstat.ctypes.data_as(up), cstat.ctypes.data_as(up), *extra)
+    n_cam, sse_cam = n_used.reshape(C_, -1).sum(axis=1), sse.reshape(C_, -1).sum(axis=1)
+    return rc, struct(cameras=cameras, camera_n_dist=self.camera_n_dist.copy(), poses=poses, sse=sse, n_used=n_used,
+                      view_status=vstat, camera_status=cstat, lm_iterations=self.lm_iterations,
+                      error=np.sqrt(sse_cam / np.maximum(n_cam, 1)), error_perview=np.sqrt(sse / np.maximum(n_used, 1)))
+
+
+def calibrate_intrinsics(point_table, boards, image_sizes, model='standard', fix_aspect=False, view_mask=None, init=None,
+                         free_dist=None, max_iterations=0):
+  """mcba_calibrate_intrinsics: the intrinsics of every camera of a detection table from its own detections, all cameras in ONE
+  device call -- what the reference gets from one cv2.calibrateCameraExtended / cv2.fisheye.calibrate per camera (camera.py:86-88,
+  camera_fisheye.py:84-86).  A view is one (frame, board) slot.
+
+  model: a name of INTRINSIC_MODELS or one per camera (a rig may mix them); fix_aspect: bool or one per camera; view_mask [C,F,B]:
+  views to use (default: board.has_min_detections, `min_detections_mask`); init: (cameras [C, 5 + n_dist], poses [C,F,B,4,4]) warm
+  start; free_dist [C, n_dist] or [n_dist]: coefficients to estimate (default: INTRINSIC_MODELS' mask), the others stay at their
+  start value; max_iterations: Levenberg-Marquardt passes (0: 100).
+
+  Returns struct(cameras [C, 5 + n_dist] blocks [fx fy cx cy skew dist...], camera_n_dist, poses [C,F,B,4,4], sse, n_used,
+  view_status [C,F,B] (VIEW_*), camera_status [C] (CAMERA_*), lm_iterations [C], error [C] = sqrt(sum sse / sum n),
+  error_perview [C,F,B] = sqrt(sse / n)).  The solution is the optimum of the reprojection cost, not cv2's (10, 1e-3) stop."""
+  boards_pts = [np.asarray(getattr(b, "points", b)) for b in boards]
+  valid = np.asarray(point_table.valid).astype(bool)
+  if view_mask is None:
+    view_mask = min_detections_mask(valid, boards)
+  inp = IntrinsicInputs(point_table.points, valid, boards_pts, image_sizes, model, fix_aspect, view_mask, init, free_dist,
+                        max_iterations)
+  rc, out = inp.call(_lib.load().mcba_calibrate_intrinsics)
+  check(rc)
+  return out

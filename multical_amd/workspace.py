@@ -1,9 +1,9 @@
 """Minimal mirror of multical.workspace.Workspace for the optimisation phase only (workspace.py:228-247).
 
-Image loading, detection, intrinsic calibration, export and the pickle checkpoint are upstream / downstream of the hot path and
-stay with the reference; a Workspace here is seeded with an initial Calibration -- given, or
-built from a detection table by `initialise_poses` (workspace.py:196-226) on the device -- and reproduces `calibrate`'s
-enable -> adjust_outliers sequence and argument mapping.
+Image loading, detection, export and the pickle checkpoint are upstream / downstream of the hot path and stay with the reference
+(SURVEY.md section 2 rows 11-16); a Workspace here is seeded with an initial Calibration -- given, or built from a detection table
+by `calibrate_single` (workspace.py:165-194) and `initialise_poses` (workspace.py:196-226) on the device -- and reproduces
+`calibrate`'s enable -> adjust_outliers sequence and argument mapping.
 """
 import numpy as np
 
@@ -29,11 +29,35 @@ class Workspace(object):
   def latest_calibration(self) -> Calibration:
     return list(self.calibrations.values())[-1]
 
-  def initialise_poses(self, point_table, boards, cameras, motion_model=StaticFrames, camera_poses=None, exclude_bad_poses=True,
+  def calibrate_single(self, point_table, boards, image_sizes, camera_model='standard', fix_aspect=False, has_skew=False,
+                       max_images=None, intrinsic_error_limit=1.0):
+    """workspace.py:165-194 from a detection table: the intrinsics of every camera from its own detections
+    (camera.calibrate_cameras: all cameras of a rejection round in one device call), stored as self.cameras.  camera_model
+    'fisheye' calibrates CameraFisheye objects (camera.calibrate_cameras_fisheye: one device call, no rejection rounds, as in the reference)."""
+    from . import camera as camera_mod
+    from .structs import struct
+    valid = np.asarray(point_table.valid).astype(bool)
+    pts = np.asarray(point_table.points)
+    C_, F, B = valid.shape[:3]
+    detections = [[[struct(ids=np.flatnonzero(valid[c, f, b]), corners=pts[c, f, b][valid[c, f, b]]) for b in range(B)]
+                   for f in range(F)] for c in range(C_)]
+    if camera_model == 'fisheye':
+      self.cameras, errs = camera_mod.calibrate_cameras_fisheye(boards, detections, image_sizes, fix_aspect=fix_aspect,
+                                                                has_skew=has_skew, max_images=max_images)
+    else:
+      self.cameras, errs = camera_mod.calibrate_cameras(boards, detections, image_sizes, intrinsic_error_limit, model=camera_model,
+                                                        fix_aspect=fix_aspect, has_skew=has_skew, max_images=max_images)
+    self.intrinsic_errors = errs
+    return self.cameras
+
+  def initialise_poses(self, point_table, boards, cameras=None, motion_model=StaticFrames, camera_poses=None, exclude_bad_poses=True,
                        pose_error_limit=1.0, names=None) -> Calibration:
     """workspace.py:196-226 from a detection table: per-view board poses (tables.make_pose_table), the pose-graph initialisation
     (tables.initialise_poses) and the initial Calibration, stored as calibrations["initialisation"].  camera_poses: {camera name:
-    4x4} like the reference's, or an array [C, 4, 4]; names: struct(camera, board, image) of name lists (default: cam0, ...)."""
+    4x4} like the reference's, or an array [C, 4, 4]; cameras=None: those of calibrate_single; names: struct(camera, board, image) of name lists (default: cam0, ...)."""
+    if cameras is None:
+      cameras = getattr(self, "cameras", None)
+      assert cameras is not None, "initialise_poses: no cameras given, first use calibrate_single"
     C_, F, B = np.asarray(point_table.valid).shape[:3]
     cam_names = list(names.camera) if names is not None else [f"cam{i}" for i in range(C_)]
     board_names = list(names.board) if names is not None else [f"board{i}" for i in range(B)]
