@@ -443,6 +443,41 @@ int32_t mcba_calibrate_intrinsics(const mcba_intrinsic_problem* p, double* camer
  * [2] kernels (start, view poses, refinement), [3] downloads + scatter; *n_views (or NULL) = views uploaded             */
 int32_t mcba_debug_calibrate_intrinsics_ms(double* ms /*[4]*/, int64_t* n_views);
 
+/* --- robot-world hand-eye start: HandEye.initialise_camera_poses / HandEyeCalibration.initialise ------------------- */
+/* cv2.calibrateRobotWorldHandEye(..., CALIB_ROBOT_WORLD_HAND_EYE_SHAH) for a batch of independent problems: find X, Z with
+ * A_i X = Z B_i over pairs of "points-transforming" poses (csrc/mcba_handeye.h: Shah's Kronecker-product closed form -- the
+ * rotations from the leading singular vectors of sum kron(R_A_i, R_B_i), the translations from a 6x6 least-squares system).
+ * The reference makes one such call per (master camera, slave camera, master board, slave board) combination of a
+ * non-overlapping rig (hand_eye/hand_eye.py:35-57 through master_slave_pair, :82-107, and hand_eye_robot_world, :110-121) and
+ * one more in HandEyeCalibration.initialise (optimization/hand_eye.py:22-36 through transform/hand_eye.py:20-50); here the pose
+ * tables go up once and the problems are index pairs, as in mcba_align_poses_indexed.  Handle-less like mcba_view_poses; same
+ * error convention, the caller owns every array.                                                                          */
+#define MCBA_HANDEYE_OK 0          /* X, Z and err are those of the closed form                                           */
+#define MCBA_HANDEYE_TOO_FEW 1     /* fewer than 3 usable pairs (hand_eye/hand_eye.py:94)                                  */
+#define MCBA_HANDEYE_DEGENERATE 2  /* the rotations do not determine (X, Z): all equal (pure translations) or about one     */
+                                   /* common axis; or non-finite input                                                     */
+typedef struct mcba_hand_eye_problem {
+  int32_t F;                      /* frames: poses per table row                                                        */
+  int64_t n_a, n_b;               /* rows of the two tables                                                             */
+  const double* table_a;          /* [n_a,F,4,4] the A side                                                             */
+  const uint8_t* valid_a;         /* [n_a,F]                                                                            */
+  const double* table_b;          /* [n_b,F,4,4] the B side; table_b == table_a and valid_b == valid_a: one upload      */
+  const uint8_t* valid_b;         /* [n_b,F]                                                                            */
+  int32_t n_problems;             /* problem p pairs row index_a[p] of A with row index_b[p] of B over every frame that  */
+  const int32_t* index_a;         /* [n_problems]                                  is valid in both                      */
+  const int32_t* index_b;         /* [n_problems]                                                                       */
+  int32_t invert_inputs;          /* != 0: every pose is inverted (rigidly) on the device before it enters --            */
+                                  /* master_slave_pair inverts the board -> camera poses (hand_eye/hand_eye.py:96-97)    */
+} mcba_hand_eye_problem;
+/* Outputs, any of which may be NULL: X [n_problems,4,4], Z [n_problems,4,4]; n_pairs [n_problems] frames that entered; status
+ * [n_problems] MCBA_HANDEYE_*; err [n_problems,F] |A_i X - Z B_i|_F of the frames that entered (transform/hand_eye.py:47-50), 0
+ * elsewhere.  Problems without a result: identities, err 0.  With the reference's argument order (world_wrt_camera,
+ * base_wrt_gripper) = (A, B): X = base_wrt_world, Z = gripper_wrt_camera.                                                  */
+int32_t mcba_hand_eye(const mcba_hand_eye_problem* p, double* X, double* Z, int32_t* n_pairs, uint8_t* status, double* err);
+/* timing of the last mcba_hand_eye call of this thread, milliseconds: [0] host preparation, [1] uploads, [2] kernel,
+ * [3] downloads; *n_problems (or NULL) = problems launched                                                              */
+int32_t mcba_debug_hand_eye_ms(double* ms /*[4]*/, int64_t* n_problems);
+
 /* --- solve -------------------------------------------------------------------------------------------------- */
 /* Trust-region least squares: replaces scipy.optimize.least_squares(method='trf', x_scale='jac', jac_sparsity=S,
  * loss, f_scale, ftol, max_nfev) at calibration.py:209-210.  x is updated in place to `res.x`.                 */

@@ -13,3 +13,5 @@ from .camera import Camera, CameraFisheye                            # noqa: F40
 from .board import Board, CharucoBoard, AprilGrid                    # noqa: F401
 from .calibration import Calibration, select_threshold, error_stats  # noqa: F401
 from .workspace import Workspace                                     # noqa: F401
+from . import hand_eye                                               # noqa: F401
+from .hand_eye import HandEyeCalibration, hand_eye_robot_world, hand_eye_robot_world_t   # noqa: F401

@@ -63,6 +63,12 @@ class ViewPoseProblem(C.Structure):   # mcba_view_pose_problem
               ("max_iterations", C.c_int32), ("lm_iterations", c_int32_p)]
 
 
+class HandEyeProblem(C.Structure):   # mcba_hand_eye_problem
+  _fields_ = [("F", C.c_int32), ("n_a", C.c_int64), ("n_b", C.c_int64), ("table_a", c_double_p), ("valid_a", c_uint8_p),
+              ("table_b", c_double_p), ("valid_b", c_uint8_p), ("n_problems", C.c_int32), ("index_a", c_int32_p),
+              ("index_b", c_int32_p), ("invert_inputs", C.c_int32)]
+
+
 class IntrinsicProblem(C.Structure):   # mcba_intrinsic_problem
   _fields_ = [("C", C.c_int32), ("F", C.c_int32), ("B", C.c_int32), ("P", C.c_int32),
               ("points", c_double_p), ("valid", c_uint8_p), ("board_points", c_double_p), ("board_sizes", c_int32_p),
@@ -106,6 +112,8 @@ SYMBOLS = [
   ("mcba_calibrate_intrinsics", C.c_int32, [C.POINTER(IntrinsicProblem), c_double_p, c_double_p, c_double_p, c_int32_p, c_uint8_p,
                                             c_uint8_p]),
   ("mcba_debug_calibrate_intrinsics_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_hand_eye", C.c_int32, [C.POINTER(HandEyeProblem), c_double_p, c_double_p, c_int32_p, c_uint8_p, c_double_p]),
+  ("mcba_debug_hand_eye_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_error_stats", C.c_int32, [H, c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), c_double_p,
                                    C.POINTER(C.c_int64), c_double_p]),
   ("mcba_error_count", C.c_int32, [H, C.c_int32, C.POINTER(C.c_int64)]),

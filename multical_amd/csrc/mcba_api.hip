@@ -38,6 +38,8 @@
 #include "mcba_init_kernels.h"
 #include "mcba_pnp_kernels.h"
 #include "mcba_pnp_driver.h"
+#include "mcba_handeye_driver.h"
+#include "mcba_handeye_kernels.h"
 #include "mcba_intrinsic_kernels.h"
 #include "mcba_intrinsic_driver.h"
 
@@ -2065,6 +2067,104 @@ int32_t mcba_debug_view_poses_ms(double* ms, int64_t* n_active) {
   REQUIRE(ms, "null argument");
   for (int i = 0; i < 4; ++i) ms[i] = g_view_pose_ms[i];
   if (n_active) *n_active = g_view_pose_active;
+  API_END
+}
+
+// ---- robot-world hand-eye start (csrc/mcba_handeye.h, k_hand_eye) ---------------------------------------------------------
+namespace {
+thread_local double g_hand_eye_ms[4] = {0.0, 0.0, 0.0, 0.0};
+thread_local int64_t g_hand_eye_problems = 0;
+
+void hand_eye(const mcba_hand_eye_problem& p, double* X, double* Z, int32_t* n_pairs, uint8_t* status, double* err) {
+  const double t0 = now_seconds();
+  handeye::Plan plan;
+  std::string msg;
+  if (!handeye::plan_problems(p, plan, msg)) throw Error(msg);
+  handeye::fill_defaults(p, plan, X, Z, n_pairs, status, err);
+  g_hand_eye_problems = 0;
+  for (double& v : g_hand_eye_ms) v = 0.0;
+  if (p.n_problems == 0 || plan.usable == 0) {   // nothing to solve: nothing is launched, the device is not touched
+    g_hand_eye_ms[0] = (now_seconds() - t0) * 1e3;
+    return;
+  }
+  hipStream_t st = resource_cache().take_stream();
+  if (st == nullptr) HIP_OK(hipStreamCreate(&st));
+  struct StreamGuard {
+    hipStream_t s;
+    ~StreamGuard() {
+      if (!resource_cache().park_stream(s)) (void)hipStreamDestroy(s);
+    }
+  } guard{st};
+  g_fill_stream = st;
+  struct ParkReset { ~ParkReset() { g_park_on_release = false; } } park_reset;   // (declared first: runs after the buffers went)
+  const size_t np_ = (size_t)p.n_problems, F = (size_t)p.F, na = (size_t)p.n_a * F, nb = (size_t)p.n_b * F;
+  DevBuf<double> d_ta, d_tb, d_out, d_err;
+  DevBuf<uint8_t> d_va, d_vb, d_status;
+  DevBuf<int32_t> d_idx, d_n;
+  d_ta.alloc(na * 16, false);
+  d_va.alloc(na, false);
+  if (!plan.same_table) {
+    d_tb.alloc(nb * 16, false);
+    d_vb.alloc(nb, false);
+  }
+  d_idx.alloc(2 * np_, false);          // index_a [np] | index_b [np]
+  d_out.alloc(np_ * 32, false);         // X [np][16] | Z [np][16]
+  d_n.alloc(np_, false);
+  d_status.alloc(np_, false);
+  if (err) d_err.alloc(np_ * F, false);
+  const double t1 = now_seconds();
+  HIP_OK(hipMemcpyAsync(d_ta.p, p.table_a, na * 16 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_va.p, p.valid_a, na, hipMemcpyHostToDevice, st));
+  if (!plan.same_table) {
+    HIP_OK(hipMemcpyAsync(d_tb.p, p.table_b, nb * 16 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_vb.p, p.valid_b, nb, hipMemcpyHostToDevice, st));
+  }
+  HIP_OK(hipMemcpyAsync(d_idx.p, p.index_a, np_ * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_idx.p + np_, p.index_b, np_ * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_OK(hipStreamSynchronize(st));
+  const double t2 = now_seconds();
+  handeye::HandEyeArgs a;
+  a.n_problems = p.n_problems; a.F = p.F; a.invert = p.invert_inputs != 0 ? 1 : 0;
+  a.table_a = d_ta.p; a.valid_a = d_va.p;
+  a.table_b = plan.same_table ? d_ta.p : d_tb.p; a.valid_b = plan.same_table ? d_va.p : d_vb.p;
+  a.index_a = d_idx.p; a.index_b = d_idx.p + np_;
+  a.X = d_out.p; a.Z = d_out.p + np_ * 16; a.n_pairs = d_n.p; a.status = d_status.p; a.err = err ? d_err.p : nullptr;
+  handeye::hand_eye_launch(a, st);
+  check_launch("k_hand_eye");
+  HIP_OK(hipStreamSynchronize(st));
+  const double t3 = now_seconds();
+  if (X) HIP_OK(hipMemcpyAsync(X, d_out.p, np_ * 16 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (Z) HIP_OK(hipMemcpyAsync(Z, d_out.p + np_ * 16, np_ * 16 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (n_pairs) HIP_OK(hipMemcpyAsync(n_pairs, d_n.p, np_ * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (status) HIP_OK(hipMemcpyAsync(status, d_status.p, np_, hipMemcpyDeviceToHost, st));
+  if (err) HIP_OK(hipMemcpyAsync(err, d_err.p, np_ * F * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  const double t4 = now_seconds();
+  g_hand_eye_problems = (int64_t)np_;
+  g_hand_eye_ms[0] = (t1 - t0) * 1e3;
+  g_hand_eye_ms[1] = (t2 - t1) * 1e3;
+  g_hand_eye_ms[2] = (t3 - t2) * 1e3;
+  g_hand_eye_ms[3] = (t4 - t3) * 1e3;
+  if (getenv("MCBA_TIMING"))
+    fprintf(stderr, "[hand_eye] %lld problems, %lld usable pairs, %d frames a row: plan %.2f ms, uploads (%.1f MB) %.2f ms, "
+            "kernel %.2f ms, downloads %.2f ms\n", (long long)np_, plan.usable, p.F, g_hand_eye_ms[0],
+            (double)((plan.same_table ? na : na + nb) * 129) / 1e6, g_hand_eye_ms[1], g_hand_eye_ms[2], g_hand_eye_ms[3]);
+  g_park_on_release = true;   // regular end: the buffers of this scope are parked for the next call of the same shape
+}
+}  // namespace
+
+int32_t mcba_hand_eye(const mcba_hand_eye_problem* p, double* X, double* Z, int32_t* n_pairs, uint8_t* status, double* err) {
+  API_BEGIN
+  REQUIRE(p, "null argument");
+  hand_eye(*p, X, Z, n_pairs, status, err);
+  API_END
+}
+
+int32_t mcba_debug_hand_eye_ms(double* ms, int64_t* n_problems) {
+  API_BEGIN
+  REQUIRE(ms, "null argument");
+  for (int i = 0; i < 4; ++i) ms[i] = g_hand_eye_ms[i];
+  if (n_problems) *n_problems = g_hand_eye_problems;
   API_END
 }
 

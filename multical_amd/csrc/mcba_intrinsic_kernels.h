@@ -25,7 +25,8 @@
 namespace mcba {
 namespace intr {
 
-typedef double intr_double4 __attribute__((ext_vector_type(4)));
+typedef pnp::wave_double4 intr_double4;
+using pnp::wave_fence;
 
 struct IntrinsicArgs {
   int P, max_iter, warm;
@@ -65,13 +66,6 @@ constexpr int L_STAGE = 0, L_PART = L_STAGE + CAL_WAVES * STAGE, L_HS = L_PART +
               L_TOTAL = L_SC + 16;
 constexpr size_t CAL_LDS_BYTES = (size_t)L_TOTAL * sizeof(double);
 static_assert(GS * GS <= STAGE, "the Gram matrix reuses the staging buffer");
-
-__device__ __forceinline__ void wave_fence() {
-  // LDS and global accesses of one wavefront complete in issue order; the fence stops the compiler from moving them across
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 template <int NPL>
 __global__ __launch_bounds__(pnp::VIEW_POSE_THREADS) void k_intrinsic_homography(IntrinsicArgs a, int n_views) {
@@ -254,8 +248,7 @@ struct DeviceBackend {
           const double X[3] = {bd[3 * j], bd[3 * j + 1], bd[3 * j + 2]};
           s += corner_sse<ND, FISH>(cam, R, p + 3, X, px[2 * j], px[2 * j + 1]);
         }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      s = pnp::wave_xor_sum(s);
       if (lane == 0) vb[VB_SSE] = s;
       wc += s;
     }

@@ -281,7 +281,8 @@ MCBA_HD void rotvec_of_matrix(const double* R, double* w) {
 
 // Cholesky solve of the packed symmetric 6x6 system (upper triangle by rows: index of (i, j), i <= j, is tri6(i, j))
 MCBA_HD constexpr int tri6(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
-MCBA_HD bool chol6_solve(const double* H /*[36] full*/, const double* rhs, double* out) {
+// (min_pivot: a pivot at or below it counts as vanished)
+MCBA_HD bool chol6_solve(const double* H /*[36] full*/, const double* rhs, double* out, double min_pivot = 0.0) {
   double Lm[36];
   MCBA_UNROLL
   for (int i = 0; i < 36; ++i) Lm[i] = 0.0;
@@ -290,7 +291,7 @@ MCBA_HD bool chol6_solve(const double* H /*[36] full*/, const double* rhs, doubl
     double d = H[j * 6 + j];
     MCBA_UNROLL
     for (int k = 0; k < j; ++k) d -= Lm[j * 6 + k] * Lm[j * 6 + k];
-    if (!(d > 0.0)) return false;
+    if (!(d > min_pivot)) return false;
     const double l = sqrt(d), il = 1.0 / l;
     Lm[j * 6 + j] = l;
     MCBA_UNROLL

@@ -36,6 +36,23 @@ struct ViewPoseArgs {
   uint8_t* status;            // [n_active]
 };
 
+// ---- wave idioms shared by the per-view / per-camera / per-problem kernels (k_view_pose, k_calibrate_camera, k_hand_eye) ----
+typedef double wave_double4 __attribute__((ext_vector_type(4)));   // accumulator of v_mfma_f64_16x16x4_f64
+
+__device__ __forceinline__ void wave_fence() {
+  // LDS and global accesses of one wavefront complete in issue order; the fence stops the compiler from moving them across
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// sum over the 64 lanes by the xor butterfly: every lane ends with the same bits
+__device__ __forceinline__ double wave_xor_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
 struct WaveReducer {
   template <int K, class Pts, class F>
   __device__ __forceinline__ void sum(const Pts& pts, F f, double* out) const {
@@ -51,12 +68,7 @@ struct WaveReducer {
         for (int k = 0; k < K; ++k) acc[k] += t[k];
       }
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-      double v = acc[k];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-      out[k] = v;
-    }
+    for (int k = 0; k < K; ++k) out[k] = wave_xor_sum(acc[k]);
   }
 };
 

@@ -224,9 +224,12 @@ def relative_between_n(table1, table2, axis=0, inv=False):
 
 def initialise_poses(pose_table, camera_poses=None):
   """tables.py:353-377: camera / board / rig-pose tables from the per-view board poses [C, F, B]."""
-  camera = estimate_relative_poses(pose_table, axis=0)
   if camera_poses is not None:
+    # (given poses replace the estimate, tables.py:357-361; the estimate is not formed first: cameras that share no view -- the
+    # rigs that NEED given poses -- have no spanning tree to estimate from)
     camera = Table.create(poses=np.asarray(camera_poses, dtype=np.float64), valid=np.ones(len(camera_poses), dtype=bool))
+  else:
+    camera = estimate_relative_poses(pose_table, axis=0)
   board = estimate_relative_poses_inv(pose_table, axis=2)
   binv = inverse(board)
   # cam @ rig @ board = pose  ->  cam @ rig = board_relative = pose @ board^-1, then one alignment per frame between the camera
@@ -245,6 +248,57 @@ def initialise_poses(pose_table, camera_poses=None):
   rig, rig_valid, _ = align_transforms_robust_ragged(p1, p2, vf.sum(axis=1), None, invert=True)
   times = Table.create(poses=rig, valid=rig_valid)
   return struct(times=times, camera=camera, board=board)
+
+
+# ---- robot-world hand-eye solves A_i X = Z B_i (hand_eye/hand_eye.py:82-121, transform/hand_eye.py:20-50) ------------------
+HANDEYE_OK, HANDEYE_TOO_FEW, HANDEYE_DEGENERATE = 0, 1, 2   # mcba.h: MCBA_HANDEYE_*
+
+
+class HandEyeInputs(object):
+  """The arrays of one mcba_hand_eye_problem, kept alive next to the ctypes struct that points into them."""
+
+  def __init__(self, table_a, valid_a, table_b, valid_b, index_a, index_b, invert=False):
+    same = table_a is table_b and valid_a is valid_b
+    self.table_a = _f64(table_a)
+    self.valid_a = np.ascontiguousarray(np.asarray(valid_a).astype(np.uint8))
+    self.table_b = self.table_a if same else _f64(table_b)
+    self.valid_b = self.valid_a if same else np.ascontiguousarray(np.asarray(valid_b).astype(np.uint8))
+    assert self.table_a.ndim == 4 and self.table_a.shape[2:] == (4, 4) and self.valid_a.shape == self.table_a.shape[:2]
+    assert self.table_b.ndim == 4 and self.table_b.shape[2:] == (4, 4) and self.valid_b.shape == self.table_b.shape[:2]
+    assert self.table_a.shape[1] == self.table_b.shape[1], "both tables hold one pose per frame"
+    self.index_a = np.ascontiguousarray(np.asarray(index_a, dtype=np.int32).reshape(-1))
+    self.index_b = np.ascontiguousarray(np.asarray(index_b, dtype=np.int32).reshape(-1))
+    assert self.index_a.shape == self.index_b.shape
+    self.n, self.F = int(self.index_a.size), int(self.table_a.shape[1])
+    self.invert = bool(invert)
+
+  def struct(self):
+    dp, up, ip = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+    s = _lib.HandEyeProblem()
+    s.F, s.n_a, s.n_b = self.F, self.table_a.shape[0], self.table_b.shape[0]
+    s.table_a, s.valid_a = self.table_a.ctypes.data_as(dp), self.valid_a.ctypes.data_as(up)
+    s.table_b, s.valid_b = self.table_b.ctypes.data_as(dp), self.valid_b.ctypes.data_as(up)
+    s.n_problems = self.n
+    s.index_a, s.index_b = self.index_a.ctypes.data_as(ip), self.index_b.ctypes.data_as(ip)
+    s.invert_inputs = 1 if self.invert else 0
+    return s
+
+  def outputs(self):
+    return (np.empty((self.n, 4, 4)), np.empty((self.n, 4, 4)), np.empty(self.n, dtype=np.int32), np.empty(self.n, dtype=np.uint8),
+            np.empty((self.n, self.F)))
+
+
+def hand_eye_batch(table_a, valid_a, table_b, valid_b, index_a, index_b, invert=False):
+  """mcba_hand_eye: problem p solves A_i X = Z B_i over the frames valid in row index_a[p] of table_a [n_a, F, 4, 4] and row
+  index_b[p] of table_b [n_b, F, 4, 4] (pass the same objects for both sides and the table is uploaded once).  invert: every
+  pose is inverted on the device first.  Returns X [n, 4, 4], Z [n, 4, 4], n_pairs [n], status [n] (HANDEYE_*), err [n, F]."""
+  inp = HandEyeInputs(table_a, valid_a, table_b, valid_b, index_a, index_b, invert)
+  X, Z, n_pairs, status, err = inp.outputs()
+  s = inp.struct()
+  dp = C.POINTER(C.c_double)
+  check(_lib.load().mcba_hand_eye(C.byref(s), X.ctypes.data_as(dp), Z.ctypes.data_as(dp), n_pairs.ctypes.data_as(C.POINTER(C.c_int32)),
+                                  status.ctypes.data_as(C.POINTER(C.c_uint8)), err.ctypes.data_as(dp)))
+  return X, Z, n_pairs, status, err
 
 
 def make_point_table(detections, boards):

@@ -51,10 +51,12 @@ class Workspace(object):
     return self.cameras
 
   def initialise_poses(self, point_table, boards, cameras=None, motion_model=StaticFrames, camera_poses=None, exclude_bad_poses=True,
-                       pose_error_limit=1.0, names=None) -> Calibration:
+                       pose_error_limit=1.0, names=None, is_non_overlapping=False) -> Calibration:
     """workspace.py:196-226 from a detection table: per-view board poses (tables.make_pose_table), the pose-graph initialisation
     (tables.initialise_poses) and the initial Calibration, stored as calibrations["initialisation"].  camera_poses: {camera name:
-    4x4} like the reference's, or an array [C, 4, 4]; cameras=None: those of calibrate_single; names: struct(camera, board, image) of name lists (default: cam0, ...)."""
+    4x4} like the reference's, or an array [C, 4, 4]; cameras=None: those of calibrate_single; names: struct(camera, board, image) of name lists (default: cam0, ...).
+    is_non_overlapping (workspace.py:204-207): without given camera_poses, the camera poses come from the robot-world hand-eye
+    start of a rig whose cameras share no board (hand_eye.HandEye: every camera pair x board pair in one device call)."""
     if cameras is None:
       cameras = getattr(self, "cameras", None)
       assert cameras is not None, "initialise_poses: no cameras given, first use calibrate_single"
@@ -65,6 +67,11 @@ class Workspace(object):
     self.pose_table = tables.make_pose_table(point_table, boards, cameras, exclude_bad_poses, pose_error_limit)
     if isinstance(camera_poses, dict):
       camera_poses = np.array([camera_poses[k] for k in cam_names])
+    if is_non_overlapping and camera_poses is None:
+      from .hand_eye import HandEye
+      self.hand_eye = HandEye(self.pose_table, cam_names)
+      cam_init = self.hand_eye.initialise_camera_poses()
+      camera_poses = np.array([cam_init[k] for k in cam_names])
     pose_init = tables.initialise_poses(self.pose_table, camera_poses=camera_poses)
     calib = Calibration(ParamList(cameras, cam_names), ParamList(boards, board_names), point_table,
                         PoseSet(pose_init.camera, cam_names), PoseSet(pose_init.board, board_names),
