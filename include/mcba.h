@@ -478,6 +478,45 @@ int32_t mcba_hand_eye(const mcba_hand_eye_problem* p, double* X, double* Z, int3
  * [3] downloads; *n_problems (or NULL) = problems launched                                                              */
 int32_t mcba_debug_hand_eye_ms(double* ms /*[4]*/, int64_t* n_problems);
 
+/* --- using a calibration: project, undistort points, undistortion maps, bicubic remap ------------------------------- */
+/* The numeric surface of the reference's Camera / CameraFisheye beyond the bundle adjustment (csrc/mcba_undistort.h: the
+ * projection of the kernels and its exact Newton inverse; maps in float32; cv2's bicubic kernel, A = -0.75, in float32 with a
+ * constant border).  Handle-less like mcba_view_poses; same error convention, the caller owns every array.  An unsupported
+ * camera family, channel count or pixel type is an error, never another route.                                          */
+typedef struct mcba_camera_set {
+  int32_t C;                      /* cameras                                                                            */
+  const double* cameras;          /* [C, 5 + n_dist] parameter blocks [fx fy cx cy skew dist...] (camera.py:144-171); the   */
+                                  /* projections read fx fy cx cy, the skew enters only the default P of the maps          */
+  int32_t n_dist;                 /* width of the dist part of every block                                              */
+  const int32_t* camera_n_dist;   /* [C] coefficients each camera really has (4, 5, 8, 12 or 14), or NULL = n_dist       */
+  const uint8_t* is_fisheye;      /* [C] Kannala-Brandt (4 coefficients) instead of Brown-Conrady, or NULL = none        */
+} mcba_camera_set;
+#define MCBA_PIXEL_U8 0
+#define MCBA_PIXEL_F32 1
+#define MCBA_UNDISTORT_OK 0             /* the inverse converged                                                         */
+#define MCBA_UNDISTORT_NOT_CONVERGED 1  /* the pixel lies outside the model's monotone range: the output is NaN            */
+/* Camera.project (camera.py:124-128, camera_fisheye.py:113-117): uv [n,2] pixels of the camera-frame points X [n,3];
+ * camera_of_point [n], or NULL = camera 0.  n == 0 launches nothing.                                                     */
+int32_t mcba_project_points(const mcba_camera_set* cams, int64_t n, const int32_t* camera_of_point, const double* X, double* uv);
+/* Camera.undistort_points (camera.py:119-122, camera_fisheye.py:108-111): out [n,2] = P [X/W, Y/W, 1], [X Y W] = R [x y 1] of
+ * the undistorted normalised point; R, P [C,3,3] or NULL (identity; the normalised point itself); status [n] MCBA_UNDISTORT_*.  */
+int32_t mcba_undistort_points(const mcba_camera_set* cams, int64_t n, const int32_t* camera_of_point, const double* uv,
+                              const double* R, const double* P, double* out, uint8_t* status);
+/* Camera.undistort_map (camera.py:113-117, camera_fisheye.py:102-106: initUndistortRectifyMap, CV_32FC2): maps [C,height,width,2]
+ * source coordinate (x, y) of every destination pixel; R [C,3,3] or NULL = identity, P [C,3,3] or NULL = the camera's own matrix.
+ * A pixel that looks behind the camera: NaN.                                                                            */
+int32_t mcba_undistort_maps(const mcba_camera_set* cams, const double* R, const double* P, int32_t width, int32_t height,
+                            float* maps);
+/* cv2.remap(image, map, None, INTER_CUBIC) (camera.py:244-246) of N images [N,Hs,Ws,channels] of one size, image i through map
+ * map_of_image[i] of maps [M,Hd,Wd,2]: dst [N,Hd,Wd,channels].  channels 1 or 3; dtype MCBA_PIXEL_*; constant border.          */
+int32_t mcba_remap(const void* src, int32_t N, int32_t Hs, int32_t Ws, int32_t channels, int32_t dtype, const float* maps,
+                   int32_t M, int32_t Hd, int32_t Wd, const int32_t* map_of_image, double border, void* dst);
+/* camera.undistort_images (camera.py:249-258) in one launch: the map coordinate is computed in registers where the remap needs
+ * it, the result is that of the remap through the undistortion maps of the same R, P, byte for byte.                    */
+int32_t mcba_undistort_images(const mcba_camera_set* cams, const double* R, const double* P, const void* src, int32_t N,
+                              int32_t Hs, int32_t Ws, int32_t channels, int32_t dtype, const int32_t* camera_of_image, int32_t Hd,
+                              int32_t Wd, double border, void* dst);
+
 /* --- solve -------------------------------------------------------------------------------------------------- */
 /* Trust-region least squares: replaces scipy.optimize.least_squares(method='trf', x_scale='jac', jac_sparsity=S,
  * loss, f_scale, ftol, max_nfev) at calibration.py:209-210.  x is updated in place to `res.x`.                 */

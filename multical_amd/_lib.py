@@ -77,6 +77,14 @@ class IntrinsicProblem(C.Structure):   # mcba_intrinsic_problem
               ("init_poses", c_double_p), ("max_iterations", C.c_int32), ("lm_iterations", c_int32_p)]
 
 
+class CameraSet(C.Structure):   # mcba_camera_set
+  _fields_ = [("C", C.c_int32), ("cameras", c_double_p), ("n_dist", C.c_int32), ("camera_n_dist", c_int32_p),
+              ("is_fisheye", c_uint8_p)]
+
+
+PIXEL_U8, PIXEL_F32 = 0, 1                            # MCBA_PIXEL_*
+UNDISTORT_OK, UNDISTORT_NOT_CONVERGED = 0, 1          # MCBA_UNDISTORT_*
+
 LOG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p)
 
@@ -114,6 +122,15 @@ SYMBOLS = [
   ("mcba_debug_calibrate_intrinsics_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_hand_eye", C.c_int32, [C.POINTER(HandEyeProblem), c_double_p, c_double_p, c_int32_p, c_uint8_p, c_double_p]),
   ("mcba_debug_hand_eye_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_project_points", C.c_int32, [C.POINTER(CameraSet), C.c_int64, c_int32_p, c_double_p, c_double_p]),
+  ("mcba_undistort_points", C.c_int32, [C.POINTER(CameraSet), C.c_int64, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                        c_uint8_p]),
+  ("mcba_undistort_maps", C.c_int32, [C.POINTER(CameraSet), c_double_p, c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
+  ("mcba_remap", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32,
+                             C.c_int32, C.c_int32, c_int32_p, C.c_double, C.c_void_p]),
+  ("mcba_undistort_images", C.c_int32, [C.POINTER(CameraSet), c_double_p, c_double_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p]),
+  ("mcba_debug_undistort_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_error_stats", C.c_int32, [H, c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), c_double_p,
                                    C.POINTER(C.c_int64), c_double_p]),
   ("mcba_error_count", C.c_int32, [H, C.c_int32, C.POINTER(C.c_int64)]),

@@ -1,8 +1,8 @@
 """Cameras as parameter blocks (multical/camera.py:27-171, multical/camera_fisheye.py:28-160).
 
-Only the bundle-adjustment face of the reference classes is mirrored: intrinsic matrix + distortion <-> parameter
-vector [fx fy | cx cy | skew | dist].  `project` lives in the HIP kernels (csrc/mcba_math.h: project_point) -- there is
-no OpenCV in this package.  Intrinsic calibration (Camera.calibrate, CameraFisheye.calibrate, calibrate_cameras: camera.py:69-105,
+The bundle-adjustment face of the reference classes: intrinsic matrix + distortion <-> parameter vector [fx fy | cx cy | skew |
+dist].  The projection lives in the HIP kernels (csrc/mcba_math.h: project_point) -- there is no OpenCV in this package; `project`,
+`undistort_points`, `undistort_map` and `undistort_images` (camera.py:113-128, 244-258) are calls into them (undistort.py).  Intrinsic calibration (Camera.calibrate, CameraFisheye.calibrate, calibrate_cameras: camera.py:69-105,
 229-241, camera_fisheye.py:71-94) runs on the device: tables.calibrate_intrinsics solves all cameras of a round in one call.
 """
 from functools import cached_property
@@ -61,6 +61,27 @@ class Camera(Parameters):
     intrinsic[:2] *= factor
     return self.copy(intrinsic=intrinsic)
 
+  def project(self, points):
+    """camera.py:124-128: pixels [..., 2] of camera-frame points [..., 3] (on the device: undistort.project_points)."""
+    from . import undistort
+    points = np.asarray(points, dtype=np.float64)
+    return undistort.project_points([self], points.reshape(-1, 3)).reshape(*points.shape[:-1], 2)
+
+  def undistort_points(self, points):
+    """camera.py:119-122 (cv2.undistortPoints(points, K, dist, P=K)): pixels [..., 2] -> the pixels of the distortion-free camera
+    with the same matrix.  The exact inverse of `project`; a pixel outside the model's range comes back NaN."""
+    from . import undistort
+    points = np.asarray(points, dtype=np.float64)
+    out, _ = undistort.undistort_points([self], points.reshape(-1, 2), P=self.intrinsic)
+    return out.reshape(*points.shape[:-1], 2)
+
+  @cached_property
+  def undistort_map(self):
+    """camera.py:113-117 (cv2.initUndistortRectifyMap(K, dist, None, K, image_size, CV_32FC2)): [H, W, 2] float32.  Cached on the
+    instance, not part of its state."""
+    from . import undistort
+    return undistort.undistort_maps([self], self.image_size)[0]
+
   def __getstate__(self):
     return dict(image_size=self.image_size, intrinsic=self.intrinsic, dist=self.dist, fix_aspect=self.fix_aspect,
                 has_skew=self.has_skew, model=self.model)
@@ -96,6 +117,28 @@ class CameraFisheye(Camera):
     cams, errs = calibrate_cameras_fisheye(boards, [detections], [image_size], max_iter=max_iter, eps=eps, model=model,
                                            fix_aspect=fix_aspect, has_skew=has_skew, flags=flags, max_images=max_images)
     return cams[0], errs[0]
+
+
+def undistort_images(images, cameras, j=None, chunksize=None):
+  """camera.py:249-258: images[c] = the images of cameras[c]; returns the undistorted images, one list per camera.
+
+  The reference maps cv2.remap(image, camera.undistort_map, None, INTER_CUBIC) over a thread pool; here every group of cameras that
+  share an image format goes to the device in ONE fused call (undistort.undistort_images: no map is materialised).  j and chunksize
+  are accepted and unused."""
+  from . import undistort
+  out = [[None] * len(cam_images) for cam_images in images]
+  groups = {}
+  for c, (camera, cam_images) in enumerate(zip(cameras, images)):
+    for i, image in enumerate(cam_images):
+      image = np.asarray(image)
+      groups.setdefault((tuple(camera.image_size), image.shape, image.dtype.str), []).append((c, i, image))
+  for (size, _, _), items in groups.items():
+    members = sorted({c for c, _, _ in items})
+    result = undistort.undistort_images([cameras[c] for c in members], np.stack([image for _, _, image in items]),
+                                        camera_of_image=[members.index(c) for c, _, _ in items], image_size=size)
+    for (c, i, _), r in zip(items, result):
+      out[c][i] = r
+  return out
 
 
 # ---- intrinsic calibration from detections (camera.py:184-241) ---------------------------------------------------------------

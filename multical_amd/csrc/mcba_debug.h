@@ -75,6 +75,10 @@ int32_t mcba_debug_observation_covariance_ms(mcba_handle h, double* ms);
 /* 1: mcba_observation_covariance takes the Sigma-route (G = That Sigma_view That^T per view), the fallback of systems whose
  * whitened panel does not fit LDS, on every rig (tests); 0 (default): automatic                                                  */
 int32_t mcba_debug_set_observation_covariance_route(mcba_handle h, int32_t sigma_route);
+/* timing of the last undistortion call of this thread (any of the five entry points of csrc/mcba_undistort.h), milliseconds:
+ * [0] uploads, [1] kernel (HIP events around the launch), [2] downloads, [3] the whole call; *n_pixels (or NULL) = destination
+ * pixels (points for the two point calls) the kernel wrote                                                                      */
+int32_t mcba_debug_undistort_ms(double* ms /*[4]*/, int64_t* n_pixels);
 
 #ifdef __cplusplus
 }

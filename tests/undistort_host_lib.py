@@ -1,0 +1,152 @@
+"""TEST INFRASTRUCTURE: ctypes wrapper of tests/undistort_host (g++ build of multical_amd/csrc/mcba_undistort.h, the mathematics of
+the undistortion entry points) + the fixtures the undistortion tests share."""
+import contextlib
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from multical_amd import _lib, undistort
+from multical_amd.camera import Camera, CameraFisheye
+
+import pnp_host_lib
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SRC = os.path.join(HERE, "undistort_host", "undistort_host.cpp")
+OUT_DIR = os.path.join(HERE, "undistort_host", "_build")
+LIB = os.path.join(OUT_DIR, "libmcba_undistort_host.so")
+NAMES = ["project_points", "undistort_points", "undistort_maps", "remap", "undistort_images"]
+# -ffp-contract=off: the host build is the plain IEEE evaluation of the formulas (the device contracts FP64 expressions to FMAs;
+# the float32 interpolation is written in explicit fmaf and must not change with this flag)
+FLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off"]
+
+
+def sources():
+  root = os.path.dirname(HERE)
+  csrc = os.path.join(root, "multical_amd", "csrc")
+  return [SRC, os.path.join(root, "include", "mcba.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
+
+
+def build(force=False):
+  os.makedirs(OUT_DIR, exist_ok=True)
+  if force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in sources()):
+    subprocess.check_call(["g++"] + FLAGS + ["-shared", "-o", LIB, SRC])
+  return LIB
+
+
+_h = None
+
+
+def lib():
+  global _h
+  if _h is None:
+    _h = C.CDLL(build())
+    _h.uh_last_error.restype = C.c_char_p
+    signatures = {name: (restype, argtypes) for name, restype, argtypes in _lib.SYMBOLS}
+    for name in NAMES:
+      fn = getattr(_h, "uh_" + name)
+      fn.restype, fn.argtypes = signatures["mcba_" + name]
+  return _h
+
+
+def entry(name):
+  """undistort._entry of the host build"""
+  fn = getattr(lib(), "uh_" + name)
+
+  def call(*args):
+    if fn(*args) != 0:
+      raise RuntimeError(lib().uh_last_error().decode())
+  return call
+
+
+@contextlib.contextmanager
+def host_backend():
+  """multical_amd.undistort (and what sits on it: Camera.undistort_map, camera.undistort_images) served by the host build"""
+  saved = undistort._entry
+  undistort._entry = entry
+  try:
+    yield undistort
+  finally:
+    undistort._entry = saved
+
+
+def on_host(fn, *args, **kwargs):
+  with host_backend():
+    return fn(*args, **kwargs)
+
+
+# ---- fixtures ------------------------------------------------------------------------------------------------------------
+# (fixture, camera): 4, 5, 8, 12 and 14 Brown-Conrady coefficients, two Kannala-Brandt cameras
+CAMERA_FIXTURES = [("tiny", 0), ("tiny_pin4", 0), ("tiny_rational", 0), ("tiny_thin_prism", 0), ("tiny_tilted", 0), ("tiny_fisheye", 0),
+                   ("tiny_fishmix", 0), ("tiny_fishmix", 1)]
+CAMERA_IDS = [f"{name}-{c}" for name, c in CAMERA_FIXTURES]
+SCALE, IMAGE_SIZE = 0.1, (200, 150)
+_cameras = {}
+
+
+def fixture_camera(name, index=0):
+  """Truth camera `index` of the golden rig, scaled to 200 x 150 (the distortion is unchanged: it acts on normalised points)."""
+  key = (name, index)
+  if key not in _cameras:
+    t = pnp_host_lib.golden_rig(name).truth.cameras[index]
+    cls = CameraFisheye if t.model == "fisheye" else Camera
+    cam = cls(image_size=t.image_size, intrinsic=t.intrinsic, dist=t.dist, model="standard" if t.model == "fisheye" else t.model)
+    _cameras[key] = cam.scale_image(SCALE).copy(image_size=IMAGE_SIZE)
+  return _cameras[key]
+
+
+def fixture_cameras():
+  return [fixture_camera(*k) for k in CAMERA_FIXTURES]
+
+
+def zoomed_out(camera, factor=0.5):
+  """the camera's matrix with factor x the focal lengths: the undistorted image looks past the edge of the source"""
+  P = np.array(camera.intrinsic, dtype=np.float64)
+  P[0, 0] *= factor
+  P[1, 1] *= factor
+  return P
+
+
+def small_rotation(deg=(3.0, -2.0, 1.5)):
+  from scipy.spatial.transform import Rotation
+  return Rotation.from_euler("xyz", deg, degrees=True).as_matrix()
+
+
+def noise_image(seed, shape, dtype=np.float32):
+  """uniform noise 0 .. 255: the strongest gradients an image can have, so the bicubic overshoot reaches both saturations"""
+  rng = np.random.default_rng(seed)
+  img = rng.uniform(0.0, 255.0, shape)
+  return np.rint(img).astype(np.uint8) if dtype == np.uint8 else img.astype(np.float32)
+
+
+def edge_coordinates(w):
+  """the coordinates every remap test covers on an axis of w pixels"""
+  return np.array([w - 1.0, -0.5, -0.25, -2.0, w + 1.0, np.nan, np.inf, -np.inf, 1e30, -1e30, 0.0, w - 0.5, -1.0, w + 0.0, -2.5,
+                   w + 0.999], dtype=np.float32)
+
+
+def random_maps(seed, M, hd, wd, hs, ws):
+  """[M, hd, wd, 2] float32: coordinates around the source (some outside), with every pair of edge coordinates planted"""
+  rng = np.random.default_rng(seed)
+  maps = np.stack([rng.uniform(-4.0, ws + 3.0, (M, hd, wd)), rng.uniform(-4.0, hs + 3.0, (M, hd, wd))], axis=-1).astype(np.float32)
+  ex, ey = edge_coordinates(ws), edge_coordinates(hs)
+  pairs = np.array([(x, y) for x in ex for y in (ey[0], ey[1], ey[5], 3.25)] + [(7.5, y) for y in ey], dtype=np.float32)
+  flat = maps.reshape(M, -1, 2)
+  n = min(len(pairs), flat.shape[1])
+  for m in range(M):
+    where = rng.choice(flat.shape[1], n, replace=False)
+    flat[m, where] = pairs[rng.permutation(len(pairs))[:n]]
+  return flat.reshape(M, hd, wd, 2)
+
+
+def ulp_distance(a, b):
+  """distance of float32 arrays in units in the last place (NaN matches NaN)"""
+  a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
+  both_nan = np.isnan(a) & np.isnan(b)
+
+  def ordered(x):
+    i = x.view(np.int32).astype(np.int64)
+    return np.where(i < 0, -(i & 0x7fffffff), i)
+  d = np.abs(ordered(a) - ordered(b))
+  return np.where(both_nan, 0, np.where(np.isnan(a) | np.isnan(b), 1 << 40, d))
