@@ -9,23 +9,9 @@
 //     ONE substitution: the regularised Gauss-Newton step that scipy gets from LSMR on a finite-difference sparse
 //     Jacobian is computed exactly from the analytic normal equations (Schur elimination of the per-frame pose blocks
 //     + dense Cholesky of the reduced system), all on the GPU.  Only 2x2 algebra and control flow run on the host.
-#include <hip/hip_runtime.h>
-#include <atomic>
-#include <algorithm>
-#include <array>
 #include <dlfcn.h>
-#include <chrono>
 #include <cmath>
-#include <complex>
-#include <cstdio>
-#include <cstring>
 #include <limits>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <stdexcept>
-#include <string>
-#include <vector>
 
 #include "../../include/mcba.h"
 #include "mcba_debug.h"
@@ -35,38 +21,23 @@
 #include "mcba_solver_kernels.h"
 #include "mcba_cov_kernels.h"
 #include "mcba_obscov_kernels.h"
-#include "mcba_init_kernels.h"
-#include "mcba_pnp_kernels.h"
-#include "mcba_pnp_driver.h"
-#include "mcba_handeye_driver.h"
-#include "mcba_handeye_kernels.h"
-#include "mcba_intrinsic_kernels.h"
-#include "mcba_intrinsic_driver.h"
-#include "mcba_undistort_driver.h"
-#include "mcba_undistort_kernels.h"
+#include "mcba_host.h"
 
 using namespace mcba;
+using namespace mcba::host;
 
-namespace {
-
+// the one definition of the host runtime's objects (mcba_host.h): every translation unit of the library shares them
+namespace mcba {
+namespace host {
 thread_local std::string g_error;
-
-struct Error : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-#define HIP_OK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) throw Error(std::string(#expr) + " failed: " + hipGetErrorString(e_));        \
-  } while (0)
-
-#define REQUIRE(cond, msg)                 \
-  do {                                     \
-    if (!(cond)) throw Error(msg);         \
-  } while (0)
-
-thread_local hipStream_t g_fill_stream = nullptr;   // stream of the running API call (see DevBuf::alloc)
+__thread hipStream_t g_fill_stream = nullptr;
+__thread bool g_park_on_release = false;
+ResourceCache& resource_cache() {
+  static ResourceCache* c = new ResourceCache();   // (never destroyed: the HIP runtime may be gone at exit)
+  return *c;
+}
+}  // namespace host
+}  // namespace mcba
 
 // Experiment / path-forcing switches (A/B variants of kernels, forcing the code paths of very large rigs on small fixtures,
 // solver traces).  The PRODUCT library does not read them from the environment: it behaves the same in every process.  Tests
@@ -79,7 +50,7 @@ static std::map<std::string, std::string>& dbg_switch_table() {
   return t;
 }
 static std::mutex g_dbg_switch_mutex;
-static const char* dbg_switch(const char* name) {
+const char* mcba::host::dbg_switch(const char* name) {
   {
     std::lock_guard<std::mutex> lock(g_dbg_switch_mutex);
     auto& t = dbg_switch_table();
@@ -92,6 +63,8 @@ static const char* dbg_switch(const char* name) {
   return nullptr;
 #endif
 }
+
+namespace {
 
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to the (function, device) pair, not to a handle: keep a process-wide
 // high-water mark per pair and only ever RAISE it, so that a second live handle with a smaller requirement cannot lower the
@@ -106,180 +79,6 @@ static void raise_dynamic_lds(const void* fn, int device, size_t bytes) {
   const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) throw std::runtime_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: ") + hipGetErrorString(e));
   cur = bytes;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Process-wide cache of the resources a handle owns.  A Workspace.calibrate creates one handle per Calibration and
-// destroys it afterwards: ~50 hipMalloc / hipFree pairs, four pinned host buffers and a stream cost more than the three
-// bundle adjustments they serve (4 ms of a 15 ms calibrate at the north-star rig).  mcba_destroy parks them here (its
-// stream is idle by then) and the next mcba_create of a problem of the same shape takes them back, exact size match only.
-// Bounded (MCBA_CACHE_MB of device memory, default 512 MB; 0 = off), emptied by the allocator before it reports
-// out-of-memory; mcba_release_cached_memory() returns everything to the runtime.
-// ---------------------------------------------------------------------------------------------------------------
-struct ResourceCache {
-  // Device memory parked for the next handle of the same shape: MCBA_CACHE_MB (default 512; 0 disables parking -- every
-  // mcba_destroy then returns its memory to the runtime).  A process that shares the GPU with torch keeps at most this
-  // much idle, and an allocation that fails with out-of-memory empties the cache and is retried once (DevBuf::alloc).
-  static size_t cache_bytes_max() {
-    static const size_t cap = [] {
-      const char* e = getenv("MCBA_CACHE_MB");
-      const long mb = e ? atol(e) : 512;
-      return (size_t)(mb > 0 ? mb : 0) << 20;
-    }();
-    return cap;
-  }
-  static constexpr size_t HOST_BYTES_MAX = 64ull << 20;
-  std::mutex m;
-  std::multimap<std::pair<int, size_t>, void*> dev, host;   // (device, bytes) -> pointer
-  std::vector<std::pair<int, hipStream_t>> streams, side_streams;
-  size_t dev_bytes = 0, host_bytes = 0;
-  static int device() {
-    int d = 0;
-    (void)hipGetDevice(&d);
-    return d;
-  }
-  void* take(std::multimap<std::pair<int, size_t>, void*>& pool, size_t& total, size_t bytes) {
-    std::lock_guard<std::mutex> lock(m);
-    auto it = pool.find({device(), bytes});
-    if (it == pool.end()) return nullptr;
-    void* p = it->second;
-    pool.erase(it);
-    total -= bytes;
-    return p;
-  }
-  // (resources are parked under the device of the handle that owned them, which need not be the caller's current device)
-  static int& park_device() {
-    static thread_local int d = -1;
-    return d;
-  }
-  bool park(std::multimap<std::pair<int, size_t>, void*>& pool, size_t& total, size_t cap, void* p, size_t bytes) {
-    std::lock_guard<std::mutex> lock(m);
-    if (total + bytes > cap) return false;
-    pool.insert({{park_device() >= 0 ? park_device() : device(), bytes}, p});
-    total += bytes;
-    return true;
-  }
-  void* take_dev(size_t bytes) { return take(dev, dev_bytes, bytes); }
-  void* take_host(size_t bytes) { return take(host, host_bytes, bytes); }
-  bool park_dev(void* p, size_t bytes) { return park(dev, dev_bytes, cache_bytes_max(), p, bytes); }
-  bool park_host(void* p, size_t bytes) { return cache_bytes_max() > 0 && park(host, host_bytes, HOST_BYTES_MAX, p, bytes); }
-  // (side = the non-blocking second stream of a handle, which carries the trial cost beside the speculative linearisation:
-  //  its own pool -- the main stream must stay a blocking stream, the synchronous copies of the API rely on that.  Creating
-  //  it anew cost every mcba_create 2-3 ms.)
-  hipStream_t take_stream(bool side = false) {
-    std::lock_guard<std::mutex> lock(m);
-    auto& pool = side ? side_streams : streams;
-    const int d = device();
-    for (size_t i = 0; i < pool.size(); ++i)
-      if (pool[i].first == d) {
-        hipStream_t s = pool[i].second;
-        pool.erase(pool.begin() + i);
-        return s;
-      }
-    return nullptr;
-  }
-  bool park_stream(hipStream_t s, bool side = false) {
-    std::lock_guard<std::mutex> lock(m);
-    auto& pool = side ? side_streams : streams;
-    if (pool.size() >= 4 || cache_bytes_max() == 0) return false;
-    pool.push_back({park_device() >= 0 ? park_device() : device(), s});
-    return true;
-  }
-  void clear() {
-    std::lock_guard<std::mutex> lock(m);
-    for (auto& e : dev) (void)hipFree(e.second);
-    for (auto& e : host) (void)hipHostFree(e.second);
-    for (auto& e : streams) (void)hipStreamDestroy(e.second);
-    for (auto& e : side_streams) (void)hipStreamDestroy(e.second);
-    dev.clear(); host.clear(); streams.clear(); side_streams.clear();
-    dev_bytes = host_bytes = 0;
-  }
-};
-ResourceCache& resource_cache() {
-  static ResourceCache* c = new ResourceCache();   // (never destroyed: the HIP runtime may be gone at exit)
-  return *c;
-}
-thread_local bool g_park_on_release = false;   // set by mcba_destroy while the handle's members go away
-
-// pinned host memory through the cache (hipHostMalloc is ~0.2 ms a call)
-void* pinned_alloc(size_t bytes) {
-  bytes = std::max<size_t>(bytes, 8);
-  if (void* p = resource_cache().take_host(bytes)) return p;
-  void* p = nullptr;
-  hipError_t e = hipHostMalloc(&p, bytes);
-  if (e == hipErrorOutOfMemory) {   // parked buffers are the first thing to give back
-    (void)hipGetLastError();
-    resource_cache().clear();
-    e = hipHostMalloc(&p, bytes);
-  }
-  if (e != hipSuccess) throw std::runtime_error(std::string("hipHostMalloc failed: ") + hipGetErrorString(e));
-  return p;
-}
-void pinned_free(void* p, size_t bytes) {
-  bytes = std::max<size_t>(bytes, 8);
-  if (p == nullptr) return;
-  if (!(g_park_on_release && resource_cache().park_host(p, bytes))) (void)hipHostFree(p);
-}
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  static size_t bytes_of(size_t count) { return (std::max<size_t>(count, 1) * sizeof(T) + 511) / 512 * 512; }
-  void release() {
-    if (p && !(g_park_on_release && resource_cache().park_dev(p, bytes_of(n)))) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  void alloc(size_t count, bool zero = true) {
-    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    if (p == nullptr || n < count) {   // (a buffer that is large enough is reused: hipFree / hipMalloc cost ~100 us each)
-      release();
-      n = count;
-      p = (T*)resource_cache().take_dev(bytes_of(count));
-      if (p == nullptr) {
-        hipError_t e = hipMalloc((void**)&p, bytes_of(count));
-        if (e == hipErrorOutOfMemory) {   // memory parked by destroyed handles must never cause an out-of-memory failure
-          (void)hipGetLastError();
-          resource_cache().clear();
-          e = hipMalloc((void**)&p, bytes_of(count));
-        }
-        if (e != hipSuccess) {
-          p = nullptr;
-          n = 0;
-          throw Error(std::string("hipMalloc of ") + std::to_string(bytes_of(count)) + " bytes failed: " + hipGetErrorString(e));
-        }
-      }
-    }
-    if (zero) {
-      // zero-fill ON THE HANDLE'S STREAM (g_fill_stream is set by every API entry that allocates): ordered against the
-      // kernels that use the buffer, no host synchronisation per buffer (mcba_create makes ~40 of them).  Without a
-      // stream: hipMemset on the NULL stream is asynchronous w.r.t. the host and not ordered against a non-blocking
-      // stream (torch.cuda.Stream) -> wait.
-      if (g_fill_stream != nullptr) {
-        HIP_OK(hipMemsetAsync(p, 0, bytes, g_fill_stream));
-      } else {
-        HIP_OK(hipMemset(p, 0, bytes));
-        HIP_OK(hipStreamSynchronize(nullptr));
-      }
-    }
-  }
-  template <typename V>
-  void upload(const V& h) {   // std::vector<T> or SlotVec<T>
-    alloc(h.size(), h.empty());
-    if (!h.empty()) HIP_OK(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  }
-};
-
-// a buffer of exactly n elements filled from the host on the call's stream (no zero-fill, no synchronisation)
-template <class T>
-void upload_async(DevBuf<T>& d, const T* h, size_t n, hipStream_t st) {
-  d.alloc(n, false);
-  HIP_OK(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, st));
 }
 
 constexpr int SEL_NEXT_BLOCKS = 256;    // workgroups (= per-block partials) of k_selm_next
@@ -623,15 +422,6 @@ int call_allreduce(mcba_handle_s* h, double* buf, size_t count, int op) {
 }
 
 
-// A kernel launch that the runtime rejects (too much dynamic LDS, a bad grid) does not throw by itself: it leaves an
-// error behind and the stream simply lacks that kernel -- the solver would go on with stale H, g or tables.  Every
-// synchronisation point of the API therefore also collects the launch status, and the launches whose LDS size / grid are
-// computed at run time check right away.
-void check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw Error(std::string("kernel launch failed (") + what + "): " + hipGetErrorString(e));
-}
-
 // MCBA_FUSED=0 forces the table form (k_tmat + k_linearize); default: the table-fed fused form wherever it applies
 void ensure_compact(mcba_handle_s* h);
 LsmrCompact compact_tables(const mcba_handle_s* h);
@@ -799,9 +589,6 @@ void fetch_scalars_begin(mcba_handle_s* h, int count, int first = 0) {
 void fetch_scalars_end(mcba_handle_s* h) {
   check_launch("iteration enqueue");
   HIP_OK(hipEventSynchronize(h->ev_fetch));
-}
-double now_seconds() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 // k_publish form of the fetch: scal[0, count) and a sequence number go to pinned host memory from a kernel on `st`; the host
 // spins on the number (falls back to a stream synchronisation after 20 ms: a failed launch must not hang the caller)
@@ -1145,23 +932,6 @@ void select_ranks_multi(mcba_handle_s* h, const uint8_t* m2, int nsel, const lon
 // =================================================================================================================
 // C ABI
 // =================================================================================================================
-// (g_fill_stream is valid for the duration of ONE API call: the entry points that allocate set it, every exit clears it)
-#define API_BEGIN try {
-#define API_END                                 \
-  g_fill_stream = nullptr;                      \
-  return 0;                                     \
-  }                                             \
-  catch (const std::exception& e) {             \
-    g_fill_stream = nullptr;                    \
-    g_error = e.what();                         \
-    return 1;                                   \
-  }                                             \
-  catch (...) {                                 \
-    g_fill_stream = nullptr;                    \
-    g_error = "unknown error";                  \
-    return 1;                                   \
-  }
-
 extern "C" {
 
 const char* mcba_last_error(void) { return g_error.c_str(); }
@@ -1715,867 +1485,6 @@ int32_t mcba_project(mcba_handle h, const double* x, double* projected) {
   h->ops->residual(d, h->t, h->stream, nullptr, nullptr, h->out_big.p, nullptr, nullptr);
   HIP_OK(hipMemcpyAsync(projected, h->out_big.p, 2 * nref * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   sync(h);
-  API_END
-}
-
-/* matrix.align_transforms_robust (transform/matrix.py:140-153) for a BATCH of problems on the device: the numeric core of
- * tables.estimate_transform (tables.py:153-176) and tables.relative_between_n (tables.py:334-345).  No handle: the
- * initialisation runs before a Calibration exists.  nA / nB = poses in A / B (ia, ib == nullptr: one per entry).
- * The stream and every buffer of a call are parked in the resource cache and taken back by the next call of the same
- * shape (an initialisation makes three calls; created and freed anew they cost 18 of its 32 ms at 16 x 1000 x 5). */
-namespace {
-void align_poses(int32_t n_problems, const int64_t* offsets, const double* A, int64_t nA, const int32_t* ia, const double* B,
-                 int64_t nB, const int32_t* ib, const uint8_t* mask, double threshold, int32_t invert, double* out,
-                 uint8_t* out_valid, uint8_t* inliers) {
-  REQUIRE(n_problems >= 0 && offsets && A && B && out && out_valid, "bad argument");
-  if (n_problems == 0) return;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    throw Error("no HIP device: the mcba back-end is GPU-only (there is no CPU fallback)");
-  const int64_t total = offsets[n_problems];
-  int64_t nmax = 1;
-  for (int p = 0; p < n_problems; ++p) {
-    REQUIRE(offsets[p + 1] >= offsets[p], "offsets must be non-decreasing");
-    nmax = std::max<int64_t>(nmax, offsets[p + 1] - offsets[p]);
-  }
-  REQUIRE(offsets[0] == 0 && total >= 0, "offsets must start at 0");
-  REQUIRE(nmax < (1ll << 24), "more than 2^24 pose pairs in one alignment problem");
-  REQUIRE((ia == nullptr) == (ib == nullptr), "both index lists or none");
-  if (ia != nullptr) {
-    REQUIRE(nA > 0 && nB > 0 && nA < (1ll << 31) && nB < (1ll << 31), "bad pose table size");
-    for (int64_t k = 0; k < total; ++k)
-      REQUIRE(ia[k] >= 0 && ia[k] < nA && ib[k] >= 0 && ib[k] < nB, "pose index out of range");
-  }
-  const bool timing = getenv("MCBA_TIMING") != nullptr;
-  const double t0 = now_seconds();
-  hipStream_t st = resource_cache().take_stream();
-  if (st == nullptr) HIP_OK(hipStreamCreate(&st));
-  struct StreamGuard {     // the stream goes back to the resource cache (it is idle: every path below synchronises or throws)
-    hipStream_t s;
-    ~StreamGuard() {
-      if (!resource_cache().park_stream(s)) (void)hipStreamDestroy(s);
-    }
-  } guard{st};
-  g_fill_stream = st;
-  {
-  struct ParkReset { ~ParkReset() { g_park_on_release = false; } } park_reset;   // (declared first: runs after the buffers went)
-  DevBuf<long long> d_off, d_prof;
-  DevBuf<double> dA, dB, d_out, d_f64;
-  DevBuf<uint8_t> d_mask, d_valid, d_inl;
-  DevBuf<int> d_i32;
-  DevBuf<int32_t> d_ia, d_ib;
-  d_off.alloc((size_t)n_problems + 1, false);
-  {
-    static_assert(sizeof(long long) == sizeof(int64_t), "offsets are copied as they are");
-    HIP_OK(hipMemcpyAsync(d_off.p, offsets, ((size_t)n_problems + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-  }
-  const size_t tot = (size_t)std::max<int64_t>(total, 1);
-  const size_t cntA = ia ? (size_t)nA : tot, cntB = ib ? (size_t)nB : tot;
-  dA.alloc(16 * cntA, false);
-  const bool same_table = ia != nullptr && A == B && nA == nB;
-  if (!same_table) dB.alloc(16 * cntB, false);
-  if (total > 0) {
-    HIP_OK(hipMemcpyAsync(dA.p, A, 16 * (ia ? (size_t)nA : (size_t)total) * sizeof(double), hipMemcpyHostToDevice, st));
-    if (!same_table) HIP_OK(hipMemcpyAsync(dB.p, B, 16 * (ib ? (size_t)nB : (size_t)total) * sizeof(double), hipMemcpyHostToDevice, st));
-    if (ia != nullptr) {
-      d_ia.alloc(tot, false);
-      d_ib.alloc(tot, false);
-      HIP_OK(hipMemcpyAsync(d_ia.p, ia, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      HIP_OK(hipMemcpyAsync(d_ib.p, ib, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    }
-  }
-  if (mask) {
-    d_mask.alloc(tot, false);
-    if (total > 0) HIP_OK(hipMemcpyAsync(d_mask.p, mask, (size_t)total, hipMemcpyHostToDevice, st));
-  }
-  d_out.alloc(16 * (size_t)n_problems, false);
-  d_valid.alloc((size_t)n_problems, false);
-  d_inl.alloc(tot, false);
-  // per-problem scratch: 14 doubles + 7 ints per entry, sized for the largest problem
-  const size_t per = (size_t)nmax, np_ = (size_t)n_problems;
-  d_f64.alloc(np_ * per * 14, false);
-  d_i32.alloc(np_ * per * 7, false);
-  AlignScratch sc;
-  sc.vec = d_f64.p;
-  sc.cen = sc.vec + np_ * per * 6;
-  sc.err = sc.cen + np_ * per * 6;
-  sc.hgt = sc.err + np_ * per;
-  sc.nd = sc.err;   // (nearest-neighbour distances of the clustering rounds: the error array is idle while a clustering runs)
-  sc.size = d_i32.p;
-  sc.chain = sc.size + np_ * per;
-  sc.rep_a = sc.chain + np_ * per;
-  sc.rep_b = sc.rep_a + np_ * per;
-  sc.parent = sc.rep_b + np_ * per;
-  sc.list = sc.parent + np_ * per;
-  sc.live = sc.list + np_ * per;
-  static const bool align_prof = dbg_switch("MCBA_ALIGN_PROF") != nullptr;
-  sc.prof = nullptr;
-  if (align_prof) {
-    d_prof.alloc(np_ * 32);
-    sc.prof = d_prof.p;
-  }
-  // dynamic LDS for the clustering state of problems with up to lds_cap selected entries (small batches of big problems get
-  // the full 125 KB; batches of many small problems only what their largest problem needs, so that several fit a CU)
-  // (a batch with a problem of more than ALIGN_LDS_CAP entries takes the full size: its error array -- 8 B per entry, up to
-  //  18 150 entries -- is ranked from LDS too)
-  const int lds_cap = (int)std::min<int64_t>(nmax, ALIGN_LDS_CAP);
-  const size_t lds = align_lds_bytes(lds_cap);
-  // (a per-DEVICE attribute: set on every call, it costs nothing next to the copies)
-  HIP_OK(hipFuncSetAttribute((const void*)k_align_robust, hipFuncAttributeMaxDynamicSharedMemorySize, (int)align_lds_bytes(ALIGN_LDS_CAP)));
-  const double t1 = now_seconds();
-  static const bool no_staged = dbg_switch("MCBA_ALIGN_MONOLITHIC") != nullptr;
-  // (the partial winners of the split scans take 24 B x ALIGN_SCAN_Z per entry and problem: batches beyond 4 M entries x problems
-  //  -- 1.6 GB of them -- stay with the one-workgroup kernel)
-  if (nmax > ALIGN_STAGED_MIN && n_problems <= 4096 && (size_t)n_problems * (size_t)nmax <= ((size_t)1 << 22) && !align_prof &&
-      !no_staged) {
-    // large problems: the rounds of the clustering as separate launches, the scans spread over the chip (k_align_stage_*)
-    DevBuf<AlignStage> d_stage;
-    DevBuf<int> d_done, d_pi;
-    DevBuf<double> d_pf;
-    d_stage.alloc(np_, true);
-    d_done.alloc(2, true);
-    d_pf.alloc(2 * np_ * ALIGN_SCAN_Z * per, false);     // partial winners of the split scans: key | d^2
-    d_pi.alloc(2 * np_ * ALIGN_SCAN_Z * per + 2 * np_ * per, false);     // slot | size; + changed | work list
-    unsigned long long* h_prog = (unsigned long long*)pinned_alloc(64);
-    struct PinGuard { unsigned long long* p; ~PinGuard() { pinned_free(p, 64); } } pin_guard{h_prog};
-    static std::atomic<unsigned long long> call_counter{0};
-    AlignArgs a;
-    a.off = d_off.p; a.A = dA.p; a.B = same_table ? dA.p : dB.p; a.ia = ia ? d_ia.p : nullptr; a.ib = ib ? d_ib.p : nullptr;
-    a.mask = mask ? d_mask.p : nullptr; a.threshold = threshold; a.invert = (int)invert; a.scratch_stride = (long long)per;
-    a.base = sc; a.out = d_out.p; a.out_valid = d_valid.p; a.inliers = d_inl.p; a.st = d_stage.p; a.done_count = d_done.p;
-    a.host_progress = h_prog;
-    a.pkey = d_pf.p; a.pd2 = d_pf.p + np_ * ALIGN_SCAN_Z * per; a.pidx = d_pi.p; a.pn = d_pi.p + np_ * ALIGN_SCAN_Z * per;
-    a.changed = d_pi.p + 2 * np_ * ALIGN_SCAN_Z * per; a.work = a.changed + np_ * per;
-    const int scan_y = (int)std::max<int64_t>(1, std::min<int64_t>(64, (nmax + 255) / 256));
-    for (int pass = 0; pass < 2; ++pass) {
-      const unsigned long long call = (++call_counter) & 0xffffull;
-      *h_prog = 0ull;
-      HIP_OK(hipMemsetAsync(d_done.p, 0, sizeof(int), st));
-      hipLaunchKernelGGL(k_align_stage_pre, dim3(n_problems), dim3(ALIGN_THREADS), 0, st, a, pass);
-      check_launch("k_align_stage_pre");
-      // rounds: enqueued a few ahead of the progress word [call | problems whose clustering ended | round] that block 0 of every
-      // merge kernel stores (kernels of finished problems return at once; at most nmax rounds can be needed)
-      constexpr int LOOKAHEAD = 8;
-      int enqueued = 0, seen_round = 0, spins = 0;
-      double t_wait = 0.0;
-      while (true) {
-        const unsigned long long w = __atomic_load_n(h_prog, __ATOMIC_ACQUIRE);
-        if ((w >> 48) == call) {
-          const int rd = (int)(w & 0xffffffull);
-          if (rd != seen_round) { seen_round = rd; t_wait = 0.0; spins = 0; }
-          if ((int)((w >> 24) & 0xffffffull) >= n_problems) break;
-        }
-        if (enqueued - seen_round < LOOKAHEAD && enqueued <= nmax + 1) {
-          hipLaunchKernelGGL(k_align_stage_scan, dim3(n_problems, scan_y, ALIGN_SCAN_Z), dim3(256), 0, st, a);
-          ++enqueued;
-          hipLaunchKernelGGL(k_align_stage_merge, dim3(n_problems), dim3(ALIGN_THREADS), 0, st, a, call, enqueued);
-          if ((enqueued & 15) == 0) check_launch("k_align_stage rounds");
-          t_wait = 0.0;
-          spins = 0;
-          continue;
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-        if ((++spins & 1023) == 0) {
-          const double now = now_seconds();
-          if (t_wait == 0.0) t_wait = now;
-          else if (now - t_wait > 0.05) {   // (a failed launch must not hang the caller)
-            HIP_OK(hipStreamSynchronize(st));
-            const unsigned long long w2 = __atomic_load_n(h_prog, __ATOMIC_ACQUIRE);
-            REQUIRE((w2 >> 48) == call && ((int)(w2 & 0xffffffull) != seen_round || (int)((w2 >> 24) & 0xffffffull) >= n_problems),
-                    "the staged alignment made no progress");
-            t_wait = 0.0;
-          }
-        }
-      }
-      hipLaunchKernelGGL(k_align_stage_post, dim3(n_problems), dim3(ALIGN_THREADS), 0, st, a, pass);
-      check_launch("k_align_stage_post");
-    }
-    HIP_OK(hipMemcpyAsync(out, d_out.p, 16 * (size_t)n_problems * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(out_valid, d_valid.p, (size_t)n_problems, hipMemcpyDeviceToHost, st));
-    if (inliers && total > 0) HIP_OK(hipMemcpyAsync(inliers, d_inl.p, (size_t)total, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    if (timing) {
-      std::vector<AlignStage> hs(np_);
-      HIP_OK(hipMemcpy(hs.data(), d_stage.p, np_ * sizeof(AlignStage), hipMemcpyDeviceToHost));
-      long long sl = 0, sw = 0, rd = 0;
-      for (const AlignStage& q : hs) { sl += q.sum_live; sw += q.sum_work; rd = std::max<long long>(rd, q.rounds); }
-      fprintf(stderr, "[align_poses] %d problems, %lld entries (staged): buffers + uploads %.2f ms, kernels + downloads %.2f ms; "
-              "rounds of the last pass <= %lld, clusters alive / scanning summed over rounds %lld / %lld\n",
-              n_problems, (long long)total, (t1 - t0) * 1e3, (now_seconds() - t1) * 1e3, rd, sl, sw);
-    }
-    g_park_on_release = true;
-    return;
-  }
-  hipLaunchKernelGGL(k_align_robust, dim3(n_problems), dim3(ALIGN_THREADS), lds, st, d_off.p, dA.p,
-                     (const double*)(same_table ? dA.p : dB.p), (const int32_t*)(ia ? d_ia.p : nullptr),
-                     (const int32_t*)(ib ? d_ib.p : nullptr), (const uint8_t*)(mask ? d_mask.p : nullptr), threshold, (int)invert,
-                     (long long)per, sc, d_out.p, d_valid.p, d_inl.p, lds_cap);
-  check_launch("k_align_robust");
-  HIP_OK(hipMemcpyAsync(out, d_out.p, 16 * (size_t)n_problems * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(out_valid, d_valid.p, (size_t)n_problems, hipMemcpyDeviceToHost, st));
-  if (inliers && total > 0) HIP_OK(hipMemcpyAsync(inliers, d_inl.p, (size_t)total, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  if (timing)
-    fprintf(stderr, "[align_poses] %d problems, %lld entries: buffers + uploads %.2f ms, kernel + downloads %.2f ms\n", n_problems,
-            (long long)total, (t1 - t0) * 1e3, (now_seconds() - t1) * 1e3);
-  if (align_prof) {   // phase cycles of the largest problem
-    std::vector<long long> hp(np_ * 32);
-    HIP_OK(hipMemcpy(hp.data(), d_prof.p, hp.size() * sizeof(long long), hipMemcpyDeviceToHost));
-    int big = 0;
-    for (int p = 1; p < n_problems; ++p)
-      if (offsets[p + 1] - offsets[p] > offsets[big + 1] - offsets[big]) big = p;
-    const char* names[9] = {"compaction", "relative poses", "robust mean", "errors", "quantile + test", "  whitening", "  clustering",
-                            "  cut+labels+mean", "  rounds (count)"};
-    for (int pass = 0; pass < 2; ++pass)
-      for (int k = 0; k < 9; ++k)
-        fprintf(stderr, "[k_align_robust] problem %d (n = %lld) pass %d %-18s %10lld\n", big,
-                (long long)(offsets[big + 1] - offsets[big]), pass, names[k], hp[(size_t)big * 32 + 16 * pass + k]);
-  }
-  g_park_on_release = true;   // regular end: the buffers of this scope are parked for the next call of the same shape
-  }
-}
-}  // namespace
-
-int32_t mcba_align_poses_robust(int32_t n_problems, const int64_t* offsets, const double* A, const double* B,
-                                const uint8_t* mask, double threshold, int32_t invert, double* out, uint8_t* out_valid,
-                                uint8_t* inliers) {
-  API_BEGIN
-  align_poses(n_problems, offsets, A, 0, nullptr, B, 0, nullptr, mask, threshold, invert, out, out_valid, inliers);
-  API_END
-}
-
-int32_t mcba_align_poses_indexed(int32_t n_problems, const int64_t* offsets, const double* table_a, int64_t n_a,
-                                 const int32_t* index_a, const double* table_b, int64_t n_b, const int32_t* index_b,
-                                 const uint8_t* mask, double threshold, int32_t invert, double* out, uint8_t* out_valid,
-                                 uint8_t* inliers) {
-  API_BEGIN
-  REQUIRE(index_a && index_b, "null index list");
-  align_poses(n_problems, offsets, table_a, n_a, index_a, table_b, n_b, index_b, mask, threshold, invert, out, out_valid, inliers);
-  API_END
-}
-
-// ---- per-view board poses (csrc/mcba_pnp.h, k_view_pose) ----------------------------------------------------------------
-namespace {
-thread_local double g_view_pose_ms[4] = {0.0, 0.0, 0.0, 0.0};
-thread_local int64_t g_view_pose_active = 0;
-
-void view_poses(const mcba_view_pose_problem& p, double* poses, double* sse, int32_t* n_used, uint8_t* status) {
-  const double t0 = now_seconds();
-  pnp::ViewPlan plan;
-  std::string err;
-  if (!pnp::plan_views(p, plan, err)) throw Error(err);
-  REQUIRE(pnp::view_pose_npl(p.P) > 0, "mcba_view_poses: boards of more than 1024 corners are not served");
-  pnp::fill_invalid(p, plan, poses, sse, n_used, status);
-  const size_t na = plan.active.size(), P = (size_t)p.P;
-  g_view_pose_active = (int64_t)na;
-  for (double& v : g_view_pose_ms) v = 0.0;
-  if (na == 0) {                       // nothing to estimate: nothing is launched, the device is not touched
-    g_view_pose_ms[0] = (now_seconds() - t0) * 1e3;
-    return;
-  }
-  hipStream_t st = resource_cache().take_stream();
-  if (st == nullptr) HIP_OK(hipStreamCreate(&st));
-  struct StreamGuard {
-    hipStream_t s;
-    ~StreamGuard() {
-      if (!resource_cache().park_stream(s)) (void)hipStreamDestroy(s);
-    }
-  } guard{st};
-  g_fill_stream = st;
-  struct ParkReset { ~ParkReset() { g_park_on_release = false; } } park_reset;   // (declared first: runs after the buffers went)
-  // the rows of the ACTIVE views only, gathered into pinned memory: the table is about 0.3 full, and a pinned source is copied
-  // without the runtime's staging pass
-  const size_t px_bytes = na * P * 2 * sizeof(double), ok_bytes = na * P, in_bytes = p.init_poses ? na * 16 * sizeof(double) : 0;
-  const size_t stage_bytes = px_bytes + in_bytes + ok_bytes;
-  char* stage = (char*)pinned_alloc(stage_bytes);
-  struct PinGuard { void* q; size_t n; ~PinGuard() { pinned_free(q, n); } } pin_guard{stage, stage_bytes};
-  double* h_px = (double*)stage;
-  double* h_in = (double*)(stage + px_bytes);
-  uint8_t* h_ok = (uint8_t*)(stage + px_bytes + in_bytes);
-  for (size_t k = 0; k < na; ++k) {
-    const size_t v = (size_t)plan.active[k];
-    memcpy(h_px + k * P * 2, p.points + v * P * 2, P * 2 * sizeof(double));
-    memcpy(h_ok + k * P, p.valid + v * P, P);
-    if (p.init_poses) memcpy(h_in + k * 16, p.init_poses + v * 16, 16 * sizeof(double));
-  }
-  DevBuf<double> d_px, d_in, d_board, d_cam, d_planes, d_out;
-  DevBuf<uint8_t> d_ok, d_fish, d_status;
-  DevBuf<int32_t> d_desc, d_nd, d_int;
-  d_px.alloc(na * P * 2, false);
-  d_ok.alloc(na * P, false);
-  if (p.init_poses) d_in.alloc(na * 16, false);
-  d_board.alloc((size_t)p.B * P * 3, false);
-  d_cam.alloc(plan.cam.size(), false);
-  d_planes.alloc(plan.planes.size(), false);
-  d_desc.alloc(2 * na, false);
-  d_nd.alloc((size_t)p.C, false);
-  d_fish.alloc((size_t)p.C, false);
-  d_out.alloc(na * 17, false);          // pose [na][16] | sse [na]
-  d_int.alloc(na * 2, false);           // n_used [na] | iterations [na]
-  d_status.alloc(na, false);
-  const double t1 = now_seconds();
-  HIP_OK(hipMemcpyAsync(d_px.p, h_px, px_bytes, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_ok.p, h_ok, ok_bytes, hipMemcpyHostToDevice, st));
-  if (p.init_poses) HIP_OK(hipMemcpyAsync(d_in.p, h_in, in_bytes, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_board.p, p.board_points, (size_t)p.B * P * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_cam.p, plan.cam.data(), plan.cam.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_planes.p, plan.planes.data(), plan.planes.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_desc.p, plan.desc.data(), 2 * na * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_nd.p, plan.cam_nd.data(), (size_t)p.C * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_fish.p, plan.cam_fish.data(), (size_t)p.C, hipMemcpyHostToDevice, st));
-  HIP_OK(hipStreamSynchronize(st));
-  const double t2 = now_seconds();
-  pnp::ViewPoseArgs a;
-  a.n_active = (int)na; a.P = p.P; a.max_iter = plan.max_iter;
-  a.pixel = d_px.p; a.valid = d_ok.p; a.desc = d_desc.p; a.init = p.init_poses ? d_in.p : nullptr; a.board = d_board.p;
-  a.cam = d_cam.p; a.cam_nd = d_nd.p; a.cam_fish = d_fish.p; a.planes = d_planes.p;
-  a.pose = d_out.p; a.sse = d_out.p + na * 16; a.n_used = d_int.p; a.iters = d_int.p + na; a.status = d_status.p;
-  pnp::view_pose_launch(a, st);
-  check_launch("k_view_pose");
-  HIP_OK(hipStreamSynchronize(st));
-  const double t3 = now_seconds();
-  std::vector<double> h_out(na * 17);
-  std::vector<int32_t> h_int(na * 2);
-  std::vector<uint8_t> h_status(na);
-  HIP_OK(hipMemcpyAsync(h_out.data(), d_out.p, na * 17 * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_int.data(), d_int.p, na * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_status.data(), d_status.p, na, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  for (size_t k = 0; k < na; ++k) {
-    const size_t v = (size_t)plan.active[k];
-    memcpy(poses + v * 16, h_out.data() + k * 16, 16 * sizeof(double));
-    sse[v] = h_out[na * 16 + k];
-    n_used[v] = h_int[k];
-    status[v] = h_status[k];
-    if (p.lm_iterations) p.lm_iterations[v] = h_int[na + k];
-  }
-  const double t4 = now_seconds();
-  g_view_pose_ms[0] = (t1 - t0) * 1e3;
-  g_view_pose_ms[1] = (t2 - t1) * 1e3;
-  g_view_pose_ms[2] = (t3 - t2) * 1e3;
-  g_view_pose_ms[3] = (t4 - t3) * 1e3;
-  if (getenv("MCBA_TIMING"))
-    fprintf(stderr, "[view_poses] %lld of %lld views, %d corners a row: plan + gather %.2f ms, uploads (%.1f MB) %.2f ms, kernel %.2f ms, "
-            "downloads + scatter %.2f ms\n", (long long)na, (long long)plan.status.size(), p.P, g_view_pose_ms[0],
-            (double)(stage_bytes) / 1e6, g_view_pose_ms[1], g_view_pose_ms[2], g_view_pose_ms[3]);
-  g_park_on_release = true;   // regular end: the buffers of this scope are parked for the next call of the same shape
-}
-}  // namespace
-
-int32_t mcba_view_poses(const mcba_view_pose_problem* p, double* poses, double* sse, int32_t* n_used, uint8_t* status) {
-  API_BEGIN
-  REQUIRE(p && poses && sse && n_used && status, "null argument");
-  view_poses(*p, poses, sse, n_used, status);
-  API_END
-}
-
-int32_t mcba_debug_view_poses_ms(double* ms, int64_t* n_active) {
-  API_BEGIN
-  REQUIRE(ms, "null argument");
-  for (int i = 0; i < 4; ++i) ms[i] = g_view_pose_ms[i];
-  if (n_active) *n_active = g_view_pose_active;
-  API_END
-}
-
-// ---- robot-world hand-eye start (csrc/mcba_handeye.h, k_hand_eye) ---------------------------------------------------------
-namespace {
-thread_local double g_hand_eye_ms[4] = {0.0, 0.0, 0.0, 0.0};
-thread_local int64_t g_hand_eye_problems = 0;
-
-void hand_eye(const mcba_hand_eye_problem& p, double* X, double* Z, int32_t* n_pairs, uint8_t* status, double* err) {
-  const double t0 = now_seconds();
-  handeye::Plan plan;
-  std::string msg;
-  if (!handeye::plan_problems(p, plan, msg)) throw Error(msg);
-  handeye::fill_defaults(p, plan, X, Z, n_pairs, status, err);
-  g_hand_eye_problems = 0;
-  for (double& v : g_hand_eye_ms) v = 0.0;
-  if (p.n_problems == 0 || plan.usable == 0) {   // nothing to solve: nothing is launched, the device is not touched
-    g_hand_eye_ms[0] = (now_seconds() - t0) * 1e3;
-    return;
-  }
-  hipStream_t st = resource_cache().take_stream();
-  if (st == nullptr) HIP_OK(hipStreamCreate(&st));
-  struct StreamGuard {
-    hipStream_t s;
-    ~StreamGuard() {
-      if (!resource_cache().park_stream(s)) (void)hipStreamDestroy(s);
-    }
-  } guard{st};
-  g_fill_stream = st;
-  struct ParkReset { ~ParkReset() { g_park_on_release = false; } } park_reset;   // (declared first: runs after the buffers went)
-  const size_t np_ = (size_t)p.n_problems, F = (size_t)p.F, na = (size_t)p.n_a * F, nb = (size_t)p.n_b * F;
-  DevBuf<double> d_ta, d_tb, d_out, d_err;
-  DevBuf<uint8_t> d_va, d_vb, d_status;
-  DevBuf<int32_t> d_idx, d_n;
-  d_ta.alloc(na * 16, false);
-  d_va.alloc(na, false);
-  if (!plan.same_table) {
-    d_tb.alloc(nb * 16, false);
-    d_vb.alloc(nb, false);
-  }
-  d_idx.alloc(2 * np_, false);          // index_a [np] | index_b [np]
-  d_out.alloc(np_ * 32, false);         // X [np][16] | Z [np][16]
-  d_n.alloc(np_, false);
-  d_status.alloc(np_, false);
-  if (err) d_err.alloc(np_ * F, false);
-  const double t1 = now_seconds();
-  HIP_OK(hipMemcpyAsync(d_ta.p, p.table_a, na * 16 * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_va.p, p.valid_a, na, hipMemcpyHostToDevice, st));
-  if (!plan.same_table) {
-    HIP_OK(hipMemcpyAsync(d_tb.p, p.table_b, nb * 16 * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_vb.p, p.valid_b, nb, hipMemcpyHostToDevice, st));
-  }
-  HIP_OK(hipMemcpyAsync(d_idx.p, p.index_a, np_ * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_idx.p + np_, p.index_b, np_ * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipStreamSynchronize(st));
-  const double t2 = now_seconds();
-  handeye::HandEyeArgs a;
-  a.n_problems = p.n_problems; a.F = p.F; a.invert = p.invert_inputs != 0 ? 1 : 0;
-  a.table_a = d_ta.p; a.valid_a = d_va.p;
-  a.table_b = plan.same_table ? d_ta.p : d_tb.p; a.valid_b = plan.same_table ? d_va.p : d_vb.p;
-  a.index_a = d_idx.p; a.index_b = d_idx.p + np_;
-  a.X = d_out.p; a.Z = d_out.p + np_ * 16; a.n_pairs = d_n.p; a.status = d_status.p; a.err = err ? d_err.p : nullptr;
-  handeye::hand_eye_launch(a, st);
-  check_launch("k_hand_eye");
-  HIP_OK(hipStreamSynchronize(st));
-  const double t3 = now_seconds();
-  if (X) HIP_OK(hipMemcpyAsync(X, d_out.p, np_ * 16 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (Z) HIP_OK(hipMemcpyAsync(Z, d_out.p + np_ * 16, np_ * 16 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (n_pairs) HIP_OK(hipMemcpyAsync(n_pairs, d_n.p, np_ * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (status) HIP_OK(hipMemcpyAsync(status, d_status.p, np_, hipMemcpyDeviceToHost, st));
-  if (err) HIP_OK(hipMemcpyAsync(err, d_err.p, np_ * F * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  const double t4 = now_seconds();
-  g_hand_eye_problems = (int64_t)np_;
-  g_hand_eye_ms[0] = (t1 - t0) * 1e3;
-  g_hand_eye_ms[1] = (t2 - t1) * 1e3;
-  g_hand_eye_ms[2] = (t3 - t2) * 1e3;
-  g_hand_eye_ms[3] = (t4 - t3) * 1e3;
-  if (getenv("MCBA_TIMING"))
-    fprintf(stderr, "[hand_eye] %lld problems, %lld usable pairs, %d frames a row: plan %.2f ms, uploads (%.1f MB) %.2f ms, "
-            "kernel %.2f ms, downloads %.2f ms\n", (long long)np_, plan.usable, p.F, g_hand_eye_ms[0],
-            (double)((plan.same_table ? na : na + nb) * 129) / 1e6, g_hand_eye_ms[1], g_hand_eye_ms[2], g_hand_eye_ms[3]);
-  g_park_on_release = true;   // regular end: the buffers of this scope are parked for the next call of the same shape
-}
-}  // namespace
-
-int32_t mcba_hand_eye(const mcba_hand_eye_problem* p, double* X, double* Z, int32_t* n_pairs, uint8_t* status, double* err) {
-  API_BEGIN
-  REQUIRE(p, "null argument");
-  hand_eye(*p, X, Z, n_pairs, status, err);
-  API_END
-}
-
-int32_t mcba_debug_hand_eye_ms(double* ms, int64_t* n_problems) {
-  API_BEGIN
-  REQUIRE(ms, "null argument");
-  for (int i = 0; i < 4; ++i) ms[i] = g_hand_eye_ms[i];
-  if (n_problems) *n_problems = g_hand_eye_problems;
-  API_END
-}
-
-// ---- using a calibration: points, undistortion maps, bicubic remap (csrc/mcba_undistort.h) ----------------------------------
-namespace {
-thread_local double g_undistort_ms[4] = {0.0, 0.0, 0.0, 0.0};
-thread_local int64_t g_undistort_pixels = 0;
-
-// what every undistortion call shares: the stream, the parked buffers, the camera tables on the device and the timing
-struct UndistortCall {
-  double t0 = now_seconds(), t_up = 0.0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  DevBuf<double> d_cam, d_iR;
-  DevBuf<int32_t> d_nd;
-  DevBuf<uint8_t> d_fish;
-
-  UndistortCall() {
-    g_undistort_pixels = 0;
-    for (double& v : g_undistort_ms) v = 0.0;
-  }
-  void open() {
-    st = resource_cache().take_stream();
-    if (st == nullptr) HIP_OK(hipStreamCreate(&st));
-    g_fill_stream = st;
-    HIP_OK(hipEventCreate(&ev[0]));
-    HIP_OK(hipEventCreate(&ev[1]));
-    t_up = now_seconds();
-  }
-  ~UndistortCall() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    d_cam.release(); d_iR.release(); d_nd.release(); d_fish.release();
-    if (st && !resource_cache().park_stream(st)) (void)hipStreamDestroy(st);
-    g_park_on_release = false;
-  }
-  undistort::CameraTable cameras(const undistort::CameraPlan& plan) {
-    upload_async(d_cam, plan.cam.data(), plan.cam.size(), st);
-    upload_async(d_nd, plan.cam_nd.data(), plan.cam_nd.size(), st);
-    upload_async(d_fish, plan.cam_fish.data(), plan.cam_fish.size(), st);
-    return undistort::CameraTable{d_cam.p, d_nd.p, d_fish.p};
-  }
-  // uploads are complete; the kernel runs between the two events
-  void begin_kernel() {
-    HIP_OK(hipStreamSynchronize(st));
-    g_undistort_ms[0] = (now_seconds() - t_up) * 1e3;
-    HIP_OK(hipEventRecord(ev[0], st));
-  }
-  double end_kernel(const char* what) {
-    check_launch(what);
-    HIP_OK(hipEventRecord(ev[1], st));
-    HIP_OK(hipStreamSynchronize(st));
-    float ms = 0.0f;
-    HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    g_undistort_ms[1] = (double)ms;
-    return now_seconds();
-  }
-  void finish(double t_down, int64_t pixels) {
-    HIP_OK(hipStreamSynchronize(st));
-    const double t = now_seconds();
-    g_undistort_ms[2] = (t - t_down) * 1e3;
-    g_undistort_ms[3] = (t - t0) * 1e3;
-    g_undistort_pixels = pixels;
-    g_park_on_release = true;   // regular end: the buffers of the call are parked for the next call of the same shape
-  }
-};
-
-void point_ops(const char* who, bool undist, const mcba_camera_set* cams, int64_t n, const int32_t* camera_of, const double* in,
-               const double* R, const double* P, double* out, uint8_t* status) {
-  UndistortCall call;              // (declared first: its end runs after the buffers of the scope went)
-  undistort::CameraPlan plan;
-  std::string err;
-  REQUIRE(n >= 0, std::string(who) + ": negative size");
-  if (!undistort::plan_cameras(cams, who, plan, err)) throw Error(err);
-  if (n == 0) return;                    // nothing is launched, the device is not touched
-  REQUIRE(in && out && (!undist || status), std::string(who) + ": null argument");
-  if (!undistort::check_camera_index(camera_of, n, cams->C, who, err)) throw Error(err);
-  const size_t N = (size_t)n, C_ = (size_t)cams->C, w = undist ? 2 : 3;
-  DevBuf<double> d_in, d_out, d_R, d_P;
-  DevBuf<int32_t> d_of;
-  DevBuf<uint8_t> d_status;
-  call.open();
-  undistort::PointOpsArgs a{};
-  a.undistort = undist ? 1 : 0;
-  a.n = n;
-  a.t = call.cameras(plan);
-  upload_async(d_in, in, N * w, call.st);
-  if (camera_of) upload_async(d_of, camera_of, N, call.st);
-  if (R) upload_async(d_R, R, C_ * 9, call.st);
-  if (P) upload_async(d_P, P, C_ * 9, call.st);
-  d_out.alloc(N * 2, false);
-  if (undist) d_status.alloc(N, false);
-  a.camera_of = camera_of ? d_of.p : nullptr;
-  a.in = d_in.p; a.R = R ? d_R.p : nullptr; a.P = P ? d_P.p : nullptr; a.out = d_out.p; a.status = undist ? d_status.p : nullptr;
-  call.begin_kernel();
-  undistort::point_ops_launch(a, call.st);
-  const double t_down = call.end_kernel("k_point_ops");
-  HIP_OK(hipMemcpyAsync(out, d_out.p, N * 2 * sizeof(double), hipMemcpyDeviceToHost, call.st));
-  if (undist) HIP_OK(hipMemcpyAsync(status, d_status.p, N, hipMemcpyDeviceToHost, call.st));
-  call.finish(t_down, n);
-}
-
-void undistort_maps(const mcba_camera_set* cams, const double* R, const double* P, int32_t width, int32_t height, float* maps) {
-  const char* who = "mcba_undistort_maps";
-  UndistortCall call;              // (declared first: its end runs after the buffers of the scope went)
-  undistort::CameraPlan plan;
-  std::vector<double> iR;
-  std::string err;
-  if (!undistort::plan_cameras(cams, who, plan, err) || !undistort::check_image_size(cams->C, height, width, who, err) ||
-      !undistort::inverse_rectifications(plan, R, P, who, iR, err))
-    throw Error(err);
-  REQUIRE(maps, "mcba_undistort_maps: null argument");
-  const size_t total = (size_t)cams->C * height * width;
-  DevBuf<float> d_maps;
-  call.open();
-  undistort::MapArgs a{};
-  a.t = call.cameras(plan);
-  upload_async(call.d_iR, iR.data(), iR.size(), call.st);
-  a.iR = call.d_iR.p; a.C = cams->C; a.H = height; a.W = width;
-  d_maps.alloc(total * 2, false);
-  a.maps = d_maps.p;
-  call.begin_kernel();
-  undistort::undistort_map_launch(a, call.st);
-  const double t_down = call.end_kernel("k_undistort_map");
-  HIP_OK(hipMemcpyAsync(maps, d_maps.p, total * 2 * sizeof(float), hipMemcpyDeviceToHost, call.st));
-  call.finish(t_down, (int64_t)total);
-}
-
-// maps != nullptr: remap through the given maps; else the fused form through the cameras
-void remap_images(const char* who, const mcba_camera_set* cams, const double* R, const double* P, const float* maps, int32_t M,
-                  const void* src, int32_t N, int32_t Hs, int32_t Ws, int32_t channels, int32_t dtype, const int32_t* index, int32_t Hd,
-                  int32_t Wd, double border, void* dst) {
-  const bool fused = maps == nullptr;
-  UndistortCall call;              // (declared first: its end runs after the buffers of the scope went)
-  undistort::CameraPlan plan;
-  std::vector<double> iR;
-  std::string err;
-  if (!undistort::check_image_format(channels, dtype, border, who, err) || !undistort::check_image_size(N, Hs, Ws, who, err) ||
-      !undistort::check_image_size(N, Hd, Wd, who, err))
-    throw Error(err);
-  if (fused) {
-    if (!undistort::plan_cameras(cams, who, plan, err) || !undistort::inverse_rectifications(plan, R, P, who, iR, err)) throw Error(err);
-    M = cams->C;
-  } else {
-    REQUIRE(M > 0, std::string(who) + ": no maps");
-  }
-  if (N == 0) return;                    // nothing is launched, the device is not touched
-  REQUIRE(src && dst && index, std::string(who) + ": null argument");
-  if (!undistort::check_camera_index(index, N, M, who, err)) throw Error(err);
-  const size_t px = undistort::pixel_bytes(dtype) * (size_t)channels;
-  const size_t src_bytes = (size_t)N * Hs * Ws * px, dst_bytes = (size_t)N * Hd * Wd * px, map_floats = fused ? 0 : (size_t)M * Hd * Wd * 2;
-  DevBuf<uint8_t> d_src, d_dst;
-  DevBuf<float> d_maps;
-  DevBuf<int32_t> d_index, d_by_camera;
-  call.open();
-  undistort::RemapArgs a{};
-  std::vector<int32_t> by_camera;        // camera_start [M + 1] | camera_images [N]
-  if (fused) {
-    a.t = call.cameras(plan);
-    upload_async(call.d_iR, iR.data(), iR.size(), call.st);
-    a.iR = call.d_iR.p;
-    a.C = M;
-    undistort::images_by_camera(index, N, M, by_camera);
-    upload_async(d_by_camera, by_camera.data(), by_camera.size(), call.st);
-    a.camera_start = d_by_camera.p;
-    a.camera_images = d_by_camera.p + M + 1;
-  } else {
-    upload_async(d_maps, maps, map_floats, call.st);
-    a.maps = d_maps.p;
-  }
-  upload_async(d_src, (const uint8_t*)src, src_bytes, call.st);
-  upload_async(d_index, index, (size_t)N, call.st);
-  d_dst.alloc(dst_bytes + undistort::REMAP_DST_SLACK, false);
-  a.src = d_src.p; a.dst = d_dst.p; a.index = d_index.p;
-  a.N = N; a.Hs = Hs; a.Ws = Ws; a.Hd = Hd; a.Wd = Wd;
-  a.border = (float)border;
-  a.flat = (Wd % 4 != 0) ? 1 : 0;
-  call.begin_kernel();
-  REQUIRE(undistort::remap_launch(a, channels, dtype, fused, call.st), std::string(who) + ": no kernel for this image format");
-  const double t_down = call.end_kernel("k_remap_cubic");
-  HIP_OK(hipMemcpyAsync(dst, d_dst.p, dst_bytes, hipMemcpyDeviceToHost, call.st));
-  call.finish(t_down, (int64_t)N * Hd * Wd);
-}
-}  // namespace
-
-int32_t mcba_project_points(const mcba_camera_set* cams, int64_t n, const int32_t* camera_of_point, const double* X, double* uv) {
-  API_BEGIN
-  point_ops("mcba_project_points", false, cams, n, camera_of_point, X, nullptr, nullptr, uv, nullptr);
-  API_END
-}
-
-int32_t mcba_undistort_points(const mcba_camera_set* cams, int64_t n, const int32_t* camera_of_point, const double* uv,
-                              const double* R, const double* P, double* out, uint8_t* status) {
-  API_BEGIN
-  point_ops("mcba_undistort_points", true, cams, n, camera_of_point, uv, R, P, out, status);
-  API_END
-}
-
-int32_t mcba_undistort_maps(const mcba_camera_set* cams, const double* R, const double* P, int32_t width, int32_t height,
-                            float* maps) {
-  API_BEGIN
-  undistort_maps(cams, R, P, width, height, maps);
-  API_END
-}
-
-int32_t mcba_remap(const void* src, int32_t N, int32_t Hs, int32_t Ws, int32_t channels, int32_t dtype, const float* maps,
-                   int32_t M, int32_t Hd, int32_t Wd, const int32_t* map_of_image, double border, void* dst) {
-  API_BEGIN
-  REQUIRE(maps, "mcba_remap: null argument");
-  remap_images("mcba_remap", nullptr, nullptr, nullptr, maps, M, src, N, Hs, Ws, channels, dtype, map_of_image, Hd, Wd, border, dst);
-  API_END
-}
-
-int32_t mcba_undistort_images(const mcba_camera_set* cams, const double* R, const double* P, const void* src, int32_t N,
-                              int32_t Hs, int32_t Ws, int32_t channels, int32_t dtype, const int32_t* camera_of_image, int32_t Hd,
-                              int32_t Wd, double border, void* dst) {
-  API_BEGIN
-  remap_images("mcba_undistort_images", cams, R, P, nullptr, 0, src, N, Hs, Ws, channels, dtype, camera_of_image, Hd, Wd, border, dst);
-  API_END
-}
-
-int32_t mcba_debug_undistort_ms(double* ms, int64_t* n_pixels) {
-  API_BEGIN
-  REQUIRE(ms, "null argument");
-  for (int i = 0; i < 4; ++i) ms[i] = g_undistort_ms[i];
-  if (n_pixels) *n_pixels = g_undistort_pixels;
-  API_END
-}
-
-// ---- intrinsic calibration (csrc/mcba_intrinsic.h, k_calibrate_camera) ---------------------------------------------------
-namespace {
-thread_local double g_intrinsic_ms[4] = {0.0, 0.0, 0.0, 0.0};
-thread_local int64_t g_intrinsic_views = 0;
-
-void calibrate_intrinsics(const mcba_intrinsic_problem& p, double* cameras, double* poses, double* sse, int32_t* n_used,
-                          uint8_t* view_status, uint8_t* camera_status) {
-  const double t0 = now_seconds();
-  intr::IntrinsicPlan plan;
-  std::string err;
-  if (!intr::plan_intrinsics(p, plan, err)) throw Error(err);
-  REQUIRE(pnp::view_pose_npl(p.P) > 0, "mcba_calibrate_intrinsics: boards of more than 1024 corners are not served");
-  intr::fill_unsolved(p, plan, cameras, poses, sse, n_used, view_status, camera_status);
-  const size_t na = plan.active.size(), P = (size_t)p.P, nc = (size_t)p.C;
-  g_intrinsic_views = (int64_t)na;
-  for (double& v : g_intrinsic_ms) v = 0.0;
-  if (na == 0) {                       // no camera to solve: nothing is uploaded or launched, the device is not touched
-    g_intrinsic_ms[0] = (now_seconds() - t0) * 1e3;
-    return;
-  }
-  hipStream_t st = resource_cache().take_stream();
-  if (st == nullptr) HIP_OK(hipStreamCreate(&st));
-  struct StreamGuard {
-    hipStream_t s;
-    ~StreamGuard() {
-      if (!resource_cache().park_stream(s)) (void)hipStreamDestroy(s);
-    }
-  } guard{st};
-  g_fill_stream = st;
-  struct ParkReset { ~ParkReset() { g_park_on_release = false; } } park_reset;   // (declared first: runs after the buffers went)
-  // the rows of the views of the cameras that are solved, gathered into pinned memory (camera-major: a camera's views are one run)
-  const size_t px_bytes = na * P * 2 * sizeof(double), ok_bytes = na * P, in_bytes = plan.warm ? na * 16 * sizeof(double) : 0;
-  const size_t stage_bytes = px_bytes + in_bytes + ok_bytes;
-  char* stage = (char*)pinned_alloc(stage_bytes);
-  struct PinGuard { void* q; size_t n; ~PinGuard() { pinned_free(q, n); } } pin_guard{stage, stage_bytes};
-  double* h_px = (double*)stage;
-  double* h_in = (double*)(stage + px_bytes);
-  uint8_t* h_ok = (uint8_t*)(stage + px_bytes + in_bytes);
-  for (size_t k = 0; k < na; ++k) {
-    const size_t v = (size_t)plan.active[k];
-    memcpy(h_px + k * P * 2, p.points + v * P * 2, P * 2 * sizeof(double));
-    memcpy(h_ok + k * P, p.valid + v * P, P);
-    if (plan.warm) memcpy(h_in + k * 16, p.init_poses + v * 16, 16 * sizeof(double));
-  }
-  std::vector<double> h_blk(nc * intr::BLK, 0.0);
-  if (plan.warm)
-    for (size_t c = 0; c < nc; ++c)
-      for (int i = 0; i < 5 + p.n_dist; ++i) h_blk[c * intr::BLK + i] = p.init_cameras[c * (5 + (size_t)p.n_dist) + i];
-  std::vector<int32_t> h_group;
-  for (const auto& g : plan.group_cameras) h_group.insert(h_group.end(), g.begin(), g.end());
-  DevBuf<double> d_px, d_pose, d_board, d_planes, d_mask, d_size, d_hv, d_blk, d_entry, d_sse, d_ws;
-  DevBuf<uint8_t> d_ok, d_fa, d_fish, d_vstatus, d_cstatus;
-  DevBuf<int32_t> d_desc, d_first, d_nd, d_int, d_group;
-  d_px.alloc(na * P * 2, false);
-  d_ok.alloc(na * P, false);
-  d_pose.alloc(na * 16, false);
-  d_board.alloc((size_t)p.B * P * 3, false);
-  d_planes.alloc(plan.planes.size(), false);
-  d_mask.alloc(plan.mask.size(), false);
-  d_size.alloc(2 * nc, false);
-  d_hv.alloc(na * 10, false);
-  d_blk.alloc(nc * intr::BLK, false);
-  d_entry.alloc(nc * CAM_STRIDE, false);
-  d_sse.alloc(na, false);
-  d_ws.alloc(na * intr::VB_STRIDE, false);
-  d_fa.alloc(nc, false);
-  d_fish.alloc(nc, false);
-  d_vstatus.alloc(na, false);
-  d_cstatus.alloc(nc, false);
-  d_desc.alloc(2 * na, false);
-  d_first.alloc(nc + 1, false);
-  d_nd.alloc(nc, false);
-  d_int.alloc(3 * na + nc, false);       // n_used [na] | iterations of the start poses [na] | usable views [na] | LM passes [C]
-  d_group.alloc(h_group.size(), false);
-  const double t1 = now_seconds();
-  HIP_OK(hipMemcpyAsync(d_px.p, h_px, px_bytes, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_ok.p, h_ok, ok_bytes, hipMemcpyHostToDevice, st));
-  if (plan.warm) HIP_OK(hipMemcpyAsync(d_pose.p, h_in, in_bytes, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_board.p, p.board_points, (size_t)p.B * P * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_planes.p, plan.planes.data(), plan.planes.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_mask.p, plan.mask.data(), plan.mask.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_size.p, plan.image_size.data(), 2 * nc * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_blk.p, h_blk.data(), h_blk.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_fa.p, plan.cam_fa.data(), nc, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_fish.p, plan.cam_fish.data(), nc, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_cstatus.p, plan.cam_status.data(), nc, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_desc.p, plan.desc.data(), 2 * na * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_first.p, plan.cam_first.data(), (nc + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_nd.p, plan.cam_nd.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_group.p, h_group.data(), h_group.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemsetAsync(d_vstatus.p, 0, na, st));                       // (warm start: every view is usable)
-  HIP_OK(hipMemsetAsync(d_int.p, 0, (3 * na + nc) * sizeof(int32_t), st));
-  HIP_OK(hipStreamSynchronize(st));
-  const double t2 = now_seconds();
-  intr::IntrinsicArgs a;
-  a.P = p.P; a.max_iter = plan.max_iter; a.warm = plan.warm ? 1 : 0;
-  a.pixel = d_px.p; a.valid = d_ok.p; a.desc = d_desc.p; a.board = d_board.p; a.planes = d_planes.p; a.cam_first = d_first.p;
-  a.cam_fa = d_fa.p; a.cam_fish = d_fish.p; a.cam_nd = d_nd.p; a.mask = d_mask.p; a.image_size = d_size.p; a.Hv = d_hv.p;
-  a.blk = d_blk.p; a.cam_entry = d_entry.p; a.pose = d_pose.p; a.vstatus = d_vstatus.p; a.sse = d_sse.p; a.n_used = d_int.p;
-  a.ws = d_ws.p; a.ulist = d_int.p + 2 * na; a.cam_iters = d_int.p + 3 * na; a.cam_status = d_cstatus.p; a.group = d_group.p;
-  if (!plan.warm) {
-    // homographies and the focal start, then the start pose of every view with that camera: k_view_pose on the resident rows
-    HIP_OK(intr::intrinsic_start_launch(a, (int)na, p.C, st));
-    pnp::ViewPoseArgs vp;
-    vp.n_active = (int)na; vp.P = p.P; vp.max_iter = 50;
-    vp.pixel = d_px.p; vp.valid = d_ok.p; vp.desc = d_desc.p; vp.init = nullptr; vp.board = d_board.p;
-    vp.cam = d_entry.p; vp.cam_nd = d_nd.p; vp.cam_fish = d_fish.p; vp.planes = d_planes.p;
-    vp.pose = d_pose.p; vp.sse = d_sse.p; vp.n_used = d_int.p; vp.iters = d_int.p + na; vp.status = d_vstatus.p;
-    pnp::view_pose_launch(vp, st);
-    check_launch("k_view_pose (intrinsic start)");
-  }
-  size_t g0 = 0;
-  for (size_t g = 0; g < plan.groups.size(); ++g) {   // one launch per camera family: a rig may mix them
-    a.group = d_group.p + g0;
-    HIP_OK(intr::calibrate_camera_launch(a, plan.groups[g].first, plan.groups[g].second != 0, (int)plan.group_cameras[g].size(), st));
-    g0 += plan.group_cameras[g].size();
-  }
-  HIP_OK(hipStreamSynchronize(st));
-  const double t3 = now_seconds();
-  std::vector<double> h_pose(na * 16), h_sse(na);
-  std::vector<int32_t> h_int(3 * na + nc);
-  std::vector<uint8_t> h_vstatus(na), h_cstatus(nc);
-  HIP_OK(hipMemcpyAsync(h_blk.data(), d_blk.p, h_blk.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_pose.data(), d_pose.p, na * 16 * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_sse.data(), d_sse.p, na * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_int.data(), d_int.p, h_int.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_vstatus.data(), d_vstatus.p, na, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_cstatus.data(), d_cstatus.p, nc, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  for (int c = 0; c < p.C; ++c) {
-    if (plan.cam_first[c + 1] == plan.cam_first[c]) continue;   // (not solved: fill_unsolved has said so)
-    camera_status[c] = h_cstatus[c];
-    if (p.lm_iterations) p.lm_iterations[c] = h_int[3 * na + c];
-    if (!intr::camera_has_result(h_cstatus[c])) {
-      intr::drop_camera_views(plan, c, poses, sse, n_used, view_status);
-      continue;
-    }
-    for (int i = 0; i < 5 + plan.cam_nd[c]; ++i) cameras[(size_t)c * (5 + p.n_dist) + i] = h_blk[(size_t)c * intr::BLK + i];
-    for (int k = plan.cam_first[c]; k < plan.cam_first[c + 1]; ++k) {
-      const size_t v = (size_t)plan.active[k];
-      view_status[v] = h_vstatus[k];
-      if (h_vstatus[k] != (uint8_t)pnp::ST_OK) continue;
-      memcpy(poses + v * 16, h_pose.data() + (size_t)k * 16, 16 * sizeof(double));
-      sse[v] = h_sse[k];
-      n_used[v] = h_int[k];
-    }
-  }
-  const double t4 = now_seconds();
-  g_intrinsic_ms[0] = (t1 - t0) * 1e3;
-  g_intrinsic_ms[1] = (t2 - t1) * 1e3;
-  g_intrinsic_ms[2] = (t3 - t2) * 1e3;
-  g_intrinsic_ms[3] = (t4 - t3) * 1e3;
-  if (getenv("MCBA_TIMING"))
-    fprintf(stderr, "[calibrate_intrinsics] %lld views of %d cameras, %d corners a row: plan + gather %.2f ms, uploads (%.1f MB) %.2f ms, "
-            "kernels %.2f ms, downloads + scatter %.2f ms\n", (long long)na, p.C, p.P, g_intrinsic_ms[0], (double)stage_bytes / 1e6,
-            g_intrinsic_ms[1], g_intrinsic_ms[2], g_intrinsic_ms[3]);
-  g_park_on_release = true;   // regular end: the buffers of this scope are parked for the next call of the same shape
-}
-}  // namespace
-
-int32_t mcba_calibrate_intrinsics(const mcba_intrinsic_problem* p, double* cameras, double* poses, double* sse, int32_t* n_used,
-                                  uint8_t* view_status, uint8_t* camera_status) {
-  API_BEGIN
-  REQUIRE(p && cameras && poses && sse && n_used && view_status && camera_status, "null argument");
-  calibrate_intrinsics(*p, cameras, poses, sse, n_used, view_status, camera_status);
-  API_END
-}
-
-int32_t mcba_debug_calibrate_intrinsics_ms(double* ms, int64_t* n_views) {
-  API_BEGIN
-  REQUIRE(ms, "null argument");
-  for (int i = 0; i < 4; ++i) ms[i] = g_intrinsic_ms[i];
-  if (n_views) *n_views = g_intrinsic_views;
   API_END
 }
 

@@ -73,10 +73,7 @@ MCBA_HD void store_pose(const double* R, const double* t, double* T) {
   T[15] = 1.0;
 }
 
-MCBA_HD void identity_pose(double* T) {
-  MCBA_UNROLL
-  for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.0 : 0.0;
-}
+using pnp::identity_pose;
 
 // a 9-vector reshaped to 3x3 -> rotation: scale by sign(det) / |det|^(1/3), then the nearest rotation
 MCBA_HD bool rotation_of_vec(const double* v, double* R) {

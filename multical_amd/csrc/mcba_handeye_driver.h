@@ -1,5 +1,5 @@
 // mcba_handeye_driver.h -- host side of mcba_hand_eye that does not touch the device: argument checks, the usable pairs of every
-// problem and the outputs of a call that launches nothing.  Shared by the API (mcba_api.hip) and the host build of the
+// problem and the outputs of a call that launches nothing.  Shared by the driver (mcba_handeye.hip) and the host build of the
 // mathematics (tests/handeye_host), so that both walk the same problems with the same inputs.
 #pragma once
 #include <stdio.h>

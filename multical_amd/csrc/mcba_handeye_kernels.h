@@ -43,7 +43,7 @@ struct HandEyeArgs {
 constexpr int HE_ROW = 18;     // vec(R_A) | vec(R_B)
 constexpr int HE_CHUNK = 64;
 
-static __global__ __launch_bounds__(64) void k_hand_eye(HandEyeArgs a) {   // (static: the header enters two translation units)
+__global__ __launch_bounds__(64) void k_hand_eye(HandEyeArgs a) {
   __shared__ double V[HE_CHUNK * HE_ROW];
   __shared__ double Gs[81];
   const int k = blockIdx.x, lane = threadIdx.x;

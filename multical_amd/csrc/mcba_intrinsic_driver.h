@@ -1,6 +1,6 @@
 // mcba_intrinsic_driver.h -- host side of mcba_calibrate_intrinsics that does not touch the device: argument checks, column masks,
-// board plane frames, the compacted list of active views per camera and the (nd, fisheye) launch groups.  Shared by the API
-// (mcba_api.hip) and the host build of the mathematics (tests/intrinsic_host), so that both walk the same views.
+// board plane frames, the compacted list of active views per camera and the (nd, fisheye) launch groups.  Shared by the driver
+// (mcba_intrinsic.hip) and the host build of the mathematics (tests/intrinsic_host), so that both walk the same views.
 #pragma once
 #include <stdio.h>
 #include <string>
@@ -9,6 +9,7 @@
 
 #include "../../include/mcba.h"
 #include "mcba_intrinsic.h"
+#include "mcba_pnp_driver.h"
 
 namespace mcba {
 namespace intr {
@@ -65,18 +66,8 @@ inline bool plan_intrinsics(const mcba_intrinsic_problem& p, IntrinsicPlan& out,
       if (!(blk[0] > 0.0) || !((out.cam_fa[c] ? blk[0] : blk[1]) > 0.0)) return fail("focal lengths of init_cameras must be positive");
     }
   }
-  out.planes.assign((size_t)p.B * pnp::PLANE_STRIDE, 0.0);
-  for (int b = 0; b < p.B; ++b) {
-    const int nb = p.board_sizes ? p.board_sizes[b] : p.P;
-    if (nb < 0 || nb > p.P) return fail("board size out of range");
-    const double dev = pnp::board_plane(p.board_points + (size_t)b * p.P * 3, nb, out.planes.data() + (size_t)b * pnp::PLANE_STRIDE);
-    if (!out.warm && !(dev <= pnp::PLANAR_TOL)) {
-      char msg[200];
-      snprintf(msg, sizeof msg, "board %d is not planar (%.3g of its extent off its plane): the homography start needs a planar "
-               "target, pass init_cameras and init_poses", b, dev);
-      return fail(msg);
-    }
-  }
+  if (!pnp::fit_board_planes(p.board_points, p.board_sizes, p.B, p.P, !out.warm, me, "init_cameras and init_poses", out.planes, err))
+    return false;
   out.view_status.assign((size_t)views, (uint8_t)pnp::ST_OK);
   out.cam_status.assign((size_t)p.C, (uint8_t)CAM_OK);
   out.active.clear();
@@ -123,8 +114,7 @@ inline void fill_unsolved(const mcba_intrinsic_problem& p, const IntrinsicPlan& 
                           int32_t* n_used, uint8_t* view_status, uint8_t* camera_status) {
   const size_t views = plan.view_status.size(), stride = 5 + (size_t)p.n_dist;
   for (size_t v = 0; v < views; ++v) {
-    double* m = poses + 16 * v;
-    for (int i = 0; i < 16; ++i) m[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    pnp::identity_pose(poses + 16 * v);
     sse[v] = 0.0;
     n_used[v] = 0;
     view_status[v] = plan.view_status[v];
@@ -141,7 +131,7 @@ inline bool camera_has_result(int status) { return status == CAM_OK || status ==
 inline void drop_camera_views(const IntrinsicPlan& plan, int c, double* poses, double* sse, int32_t* n_used, uint8_t* view_status) {
   for (int k = plan.cam_first[c]; k < plan.cam_first[c + 1]; ++k) {
     const size_t v = (size_t)plan.active[k];
-    for (int i = 0; i < 16; ++i) poses[16 * v + i] = (i % 5 == 0) ? 1.0 : 0.0;
+    pnp::identity_pose(poses + 16 * v);
     sse[v] = 0.0;
     n_used[v] = 0;
     view_status[v] = (uint8_t)pnp::ST_MASKED;

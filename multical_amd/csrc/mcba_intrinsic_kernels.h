@@ -84,7 +84,7 @@ __global__ __launch_bounds__(pnp::VIEW_POSE_THREADS) void k_intrinsic_homography
   }
 }
 
-static __global__ __launch_bounds__(64) void k_intrinsic_focal(IntrinsicArgs a) {   // (static: the header enters two translation units)
+__global__ __launch_bounds__(64) void k_intrinsic_focal(IntrinsicArgs a) {
   const int c = blockIdx.x, k0 = a.cam_first[c], nv = a.cam_first[c + 1] - k0;
   if (nv <= 0 || threadIdx.x != 0) return;
   double* blk = a.blk + (size_t)c * BLK;

@@ -84,6 +84,12 @@ MCBA_HD bool supported_model(int nd, bool fisheye) {
   return fisheye ? nd >= 4 : (nd == 4 || nd == 5 || nd == 8 || nd == 12 || nd == 14);
 }
 
+// the pose of everything that has no result: row-major 4x4 identity
+MCBA_HD void identity_pose(double* T) {
+  MCBA_UNROLL
+  for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.0 : 0.0;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // corner containers.  size() slots per "lane"; slot i of lane l holds corner l + lanes * i of the table slot.
 //   x, y      undistorted normalised image point          X, Y, Z   board point (board frame)

@@ -1,4 +1,7 @@
-// translation unit of k_view_pose (mcba_pnp_kernels.h): the three register-array sizes, camera family switched at run time
+// translation unit of k_view_pose (mcba_pnp_kernels.h): the three register-array sizes, camera family switched at run time;
+// and the host driver of mcba_view_poses
+#include "mcba_host.h"
+#include "mcba_pnp_driver.h"
 #include "mcba_pnp_kernels.h"
 
 namespace mcba {
@@ -17,3 +20,88 @@ void view_pose_launch(const ViewPoseArgs& a, hipStream_t st) {
 
 }  // namespace pnp
 }  // namespace mcba
+
+using namespace mcba;
+using namespace mcba::host;
+
+extern "C" {
+
+namespace {
+thread_local CallTiming g_view_pose_timing;   // plan + gather | uploads | kernel | downloads + scatter; active views
+
+void view_poses(const mcba_view_pose_problem& p, double* poses, double* sse, int32_t* n_used, uint8_t* status) {
+  DeviceCall call(g_view_pose_timing);   // (before the buffers: see the type)
+  pnp::ViewPlan plan;
+  std::string err;
+  if (!pnp::plan_views(p, plan, err)) throw Error(err);
+  REQUIRE(pnp::view_pose_npl(p.P) > 0, "mcba_view_poses: boards of more than 1024 corners are not served");
+  pnp::fill_invalid(p, plan, poses, sse, n_used, status);
+  const size_t na = plan.active.size(), P = (size_t)p.P;
+  call.tm.reset((int64_t)na);
+  if (na == 0) return call.record();   // nothing to estimate: nothing is launched, the device is not touched
+  call.open();
+  const hipStream_t st = call.st;
+  pnp::ActiveRows rows(na, P, p.init_poses != nullptr);
+  PinnedBuf pinned(rows.bytes());
+  rows.gather(pinned.p, plan.active, P, p.points, p.valid, p.init_poses);
+  // d_out: pose [na][16] | sse [na]; d_int: n_used [na] | iterations [na]
+  DevBuf<double> d_px(na * P * 2), d_in, d_board((size_t)p.B * P * 3), d_cam(plan.cam.size()), d_planes(plan.planes.size()), d_out(na * 17);
+  DevBuf<uint8_t> d_ok(na * P), d_fish((size_t)p.C), d_status(na);
+  DevBuf<int32_t> d_desc(2 * na), d_nd((size_t)p.C), d_int(na * 2);
+  if (p.init_poses) d_in.alloc(na * 16, false);
+  call.stamp();
+  HIP_OK(hipMemcpyAsync(d_px.p, rows.px, rows.px_bytes, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_ok.p, rows.ok, rows.ok_bytes, hipMemcpyHostToDevice, st));
+  if (p.init_poses) HIP_OK(hipMemcpyAsync(d_in.p, rows.in, rows.in_bytes, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_board.p, p.board_points, (size_t)p.B * P * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_cam.p, plan.cam.data(), plan.cam.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_planes.p, plan.planes.data(), plan.planes.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_desc.p, plan.desc.data(), 2 * na * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_nd.p, plan.cam_nd.data(), (size_t)p.C * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(d_fish.p, plan.cam_fish.data(), (size_t)p.C, hipMemcpyHostToDevice, st));
+  HIP_OK(hipStreamSynchronize(st));
+  call.stamp();
+  pnp::ViewPoseArgs a;
+  a.n_active = (int)na; a.P = p.P; a.max_iter = plan.max_iter;
+  a.pixel = d_px.p; a.valid = d_ok.p; a.desc = d_desc.p; a.init = p.init_poses ? d_in.p : nullptr; a.board = d_board.p;
+  a.cam = d_cam.p; a.cam_nd = d_nd.p; a.cam_fish = d_fish.p; a.planes = d_planes.p;
+  a.pose = d_out.p; a.sse = d_out.p + na * 16; a.n_used = d_int.p; a.iters = d_int.p + na; a.status = d_status.p;
+  pnp::view_pose_launch(a, st);
+  check_launch("k_view_pose");
+  HIP_OK(hipStreamSynchronize(st));
+  call.stamp();
+  std::vector<double> h_out(na * 17);
+  std::vector<int32_t> h_int(na * 2);
+  std::vector<uint8_t> h_status(na);
+  HIP_OK(hipMemcpyAsync(h_out.data(), d_out.p, na * 17 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(h_int.data(), d_int.p, na * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(h_status.data(), d_status.p, na, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  for (size_t k = 0; k < na; ++k) {
+    const size_t v = (size_t)plan.active[k];
+    memcpy(poses + v * 16, h_out.data() + k * 16, 16 * sizeof(double));
+    sse[v] = h_out[na * 16 + k];
+    n_used[v] = h_int[k];
+    status[v] = h_status[k];
+    if (p.lm_iterations) p.lm_iterations[v] = h_int[na + k];
+  }
+  call.record();
+  const double* ms = call.tm.ms;
+  if (getenv("MCBA_TIMING"))
+    fprintf(stderr, "[view_poses] %lld of %lld views, %d corners a row: plan + gather %.2f ms, uploads (%.1f MB) %.2f ms, kernel %.2f ms, "
+            "downloads + scatter %.2f ms\n", (long long)na, (long long)plan.status.size(), p.P, ms[0],
+            (double)rows.bytes() / 1e6, ms[1], ms[2], ms[3]);
+  call.finish();
+}
+}  // namespace
+
+int32_t mcba_view_poses(const mcba_view_pose_problem* p, double* poses, double* sse, int32_t* n_used, uint8_t* status) {
+  API_BEGIN
+  REQUIRE(p && poses && sse && n_used && status, "null argument");
+  view_poses(*p, poses, sse, n_used, status);
+  API_END
+}
+
+}  // extern "C"
+
+MCBA_TIMING_GETTER(mcba_debug_view_poses_ms, g_view_pose_timing)

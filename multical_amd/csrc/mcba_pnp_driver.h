@@ -1,8 +1,9 @@
 // mcba_pnp_driver.h -- host side of mcba_view_poses that does not touch the device: argument checks, camera entries, board plane
-// frames and the list of active views.  Shared by the API (mcba_api.hip) and the host build of the per-view mathematics
+// frames and the list of active views.  Shared by the driver (mcba_pnp.hip) and the host build of the per-view mathematics
 // (tests/pnp_host), so that both walk the same views with the same inputs.
 #pragma once
 #include <stdio.h>
+#include <string.h>
 #include <string>
 #include <vector>
 
@@ -22,6 +23,27 @@ struct ViewPlan {
   std::vector<uint8_t> status;      // [C F B] MCBA_VIEW_MASKED / TOO_FEW of the views that are not estimated (else OK)
   int max_iter = 50;
 };
+
+// The plane frame of every board ([B][PLANE_STRIDE]; board_sizes: corners of every board, or null = P).  need_planar: the call
+// starts from homographies, so a board that leaves its plane by more than PLANAR_TOL of its extent is refused, with the
+// arguments that would serve it (`advice`) in the message.  Shared with mcba_calibrate_intrinsics (mcba_intrinsic_driver.h).
+inline bool fit_board_planes(const double* board_points, const int32_t* board_sizes, int B, int P, bool need_planar, const char* who,
+                             const char* advice, std::vector<double>& planes, std::string& err) {
+  planes.assign((size_t)B * PLANE_STRIDE, 0.0);
+  for (int b = 0; b < B; ++b) {
+    const int nb = board_sizes ? board_sizes[b] : P;
+    if (nb < 0 || nb > P) { err = std::string(who) + ": board size out of range"; return false; }
+    const double dev = board_plane(board_points + (size_t)b * P * 3, nb, planes.data() + (size_t)b * PLANE_STRIDE);
+    if (need_planar && !(dev <= PLANAR_TOL)) {
+      char msg[256];
+      snprintf(msg, sizeof msg, "%s: board %d is not planar (%.3g of its extent off its plane): the homography start needs a planar "
+               "target, pass %s", who, b, dev, advice);
+      err = msg;
+      return false;
+    }
+  }
+  return true;
+}
 
 inline bool plan_views(const mcba_view_pose_problem& p, ViewPlan& out, std::string& err) {
   if (p.C <= 0 || p.F <= 0 || p.B <= 0 || p.P <= 0) { err = "mcba_view_poses: C, F, B, P must be positive"; return false; }
@@ -50,19 +72,8 @@ inline bool plan_views(const mcba_view_pose_problem& p, ViewPlan& out, std::stri
     out.cam_nd[c] = nd;
     out.cam_fish[c] = fish ? 1 : 0;
   }
-  out.planes.assign((size_t)p.B * PLANE_STRIDE, 0.0);
-  for (int b = 0; b < p.B; ++b) {
-    const int nb = p.board_sizes ? p.board_sizes[b] : p.P;
-    if (nb < 0 || nb > p.P) { err = "mcba_view_poses: board size out of range"; return false; }
-    const double dev = board_plane(p.board_points + (size_t)b * p.P * 3, nb, out.planes.data() + (size_t)b * PLANE_STRIDE);
-    if (!p.init_poses && !(dev <= PLANAR_TOL)) {
-      char msg[200];
-      snprintf(msg, sizeof msg, "mcba_view_poses: board %d is not planar (%.3g of its extent off its plane): the homography start "
-               "needs a planar target, pass init_poses", b, dev);
-      err = msg;
-      return false;
-    }
-  }
+  if (!fit_board_planes(p.board_points, p.board_sizes, p.B, p.P, !p.init_poses, "mcba_view_poses", "init_poses", out.planes, err))
+    return false;
   out.status.assign((size_t)views, (uint8_t)ST_OK);
   out.active.clear();
   out.desc.clear();
@@ -80,13 +91,34 @@ inline bool plan_views(const mcba_view_pose_problem& p, ViewPlan& out, std::stri
   return true;
 }
 
+// The rows of the ACTIVE views only, gathered into one staging buffer the driver supplies (pinned: the table is about 0.3 full, and
+// a pinned source is copied without the runtime's staging pass): pixels [na][P][2] | start poses [na][16] or none | valid [na][P]
+struct ActiveRows {
+  size_t px_bytes, in_bytes, ok_bytes;
+  double *px = nullptr, *in = nullptr;
+  uint8_t* ok = nullptr;
+  ActiveRows(size_t na, size_t P, bool with_poses)
+      : px_bytes(na * P * 2 * sizeof(double)), in_bytes(with_poses ? na * 16 * sizeof(double) : 0), ok_bytes(na * P) {}
+  size_t bytes() const { return px_bytes + in_bytes + ok_bytes; }
+  void gather(void* stage, const std::vector<int32_t>& active, size_t P, const double* points, const uint8_t* valid, const double* poses) {
+    px = (double*)stage;
+    in = (double*)((char*)stage + px_bytes);
+    ok = (uint8_t*)stage + px_bytes + in_bytes;
+    for (size_t k = 0; k < active.size(); ++k) {
+      const size_t v = (size_t)active[k];
+      memcpy(px + k * P * 2, points + v * P * 2, P * 2 * sizeof(double));
+      memcpy(ok + k * P, valid + v * P, P);
+      if (in_bytes) memcpy(in + k * 16, poses + v * 16, 16 * sizeof(double));
+    }
+  }
+};
+
 // outputs of the views that are not estimated (and the default of those that are)
 inline void fill_invalid(const mcba_view_pose_problem& p, const ViewPlan& plan, double* poses, double* sse, int32_t* n_used,
                          uint8_t* status) {
   const size_t views = plan.status.size();
   for (size_t v = 0; v < views; ++v) {
-    double* m = poses + 16 * v;
-    for (int i = 0; i < 16; ++i) m[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    identity_pose(poses + 16 * v);
     sse[v] = 0.0;
     n_used[v] = 0;
     status[v] = plan.status[v];

@@ -1,5 +1,5 @@
 // mcba_undistort_driver.h -- host side of the undistortion entry points that does not touch the device: argument checks, camera
-// entries and the inverse rectification matrices iR = (P R)^-1.  Shared by the API (mcba_api.hip) and the host build of the
+// entries and the inverse rectification matrices iR = (P R)^-1.  Shared by the driver (mcba_undistort.hip) and the host build of the
 // mathematics (tests/undistort_host), so that both serve the same calls with the same tables.
 #pragma once
 #include <math.h>

@@ -67,7 +67,7 @@ struct RemapArgs {
 constexpr int UNDISTORT_THREADS = 256;
 constexpr int TILE_W = 256, TILE_H = UNDISTORT_THREADS / 64;
 
-static __global__ __launch_bounds__(UNDISTORT_THREADS) void k_point_ops(PointOpsArgs a) {
+__global__ __launch_bounds__(UNDISTORT_THREADS) void k_point_ops(PointOpsArgs a) {
   const long long stride = (long long)gridDim.x * UNDISTORT_THREADS;
   for (long long i = (long long)blockIdx.x * UNDISTORT_THREADS + threadIdx.x; i < a.n; i += stride) {
     const int c = a.camera_of ? a.camera_of[i] : 0;
@@ -88,7 +88,7 @@ static __global__ __launch_bounds__(UNDISTORT_THREADS) void k_point_ops(PointOps
   }
 }
 
-static __global__ __launch_bounds__(UNDISTORT_THREADS) void k_undistort_map(MapArgs a) {
+__global__ __launch_bounds__(UNDISTORT_THREADS) void k_undistort_map(MapArgs a) {
   const long long per = (long long)a.H * a.W, total = per * a.C;
   const long long stride = (long long)gridDim.x * UNDISTORT_THREADS;
   for (long long i = (long long)blockIdx.x * UNDISTORT_THREADS + threadIdx.x; i < total; i += stride) {

@@ -27,20 +27,26 @@ INVERSE = [("s_cmp_eq", "s_cmp_lg"), ("s_cmp_lt", "s_cmp_ge"), ("s_cmp_gt", "s_c
            ("s_cbranch_vccz", "s_cbranch_vccnz"), ("s_cbranch_execz", "s_cbranch_execnz")]
 
 
+def symbol(name):
+  """(a kernel of internal linkage carries an L before its own name, _ZN4mcba7handeyeL10k_hand_eye..: static or not, it is the same kernel)"""
+  return re.sub(r"L(\d+k_)", r"\1", name)
+
+
 def listings(build_dir):
-  """kernel symbol -> list of instruction lines (comments and directives dropped, labels kept out)"""
+  """kernel symbol -> {unit: list of instruction lines} (comments and directives dropped, labels kept out).  The symbol alone
+  is the key: a kernel that moved to another translation unit is the same kernel."""
   out = {}
   for path in sorted(glob.glob(os.path.join(build_dir, "*-gfx950.s"))):
     name, body = None, []
     for line in open(path):
       m = re.match(r"^(\w+):", line)
       if m and not line.startswith(".L"):
-        name, body = m.group(1), []
+        name, body = symbol(m.group(1)), []
         continue
       if name is None:
         continue
       if line.startswith(".Lfunc_end"):
-        out[(os.path.basename(path).split("-hip-")[0], name)] = body
+        out.setdefault(name, {})[os.path.basename(path).split("-hip-")[0]] = body
         name = None
         continue
       text = line.split(";")[0].strip()
@@ -51,14 +57,14 @@ def listings(build_dir):
 
 
 def kernels_of(build_dir):
-  """the kernel descriptor symbols of the build's listings"""
-  names = set()
+  """the kernel descriptor symbols of the build's listings -> the units that emit them"""
+  names = {}
   for path in glob.glob(os.path.join(build_dir, "*-gfx950.s")):
     unit = os.path.basename(path).split("-hip-")[0]
     for line in open(path):
       m = re.match(r"^\s*\.amdhsa_kernel\s+(\w+)", line)
       if m:
-        names.add((unit, m.group(1)))
+        names.setdefault(symbol(m.group(1)), []).append(unit)
   return names
 
 
@@ -68,7 +74,7 @@ def resources(log):
   for line in open(log):
     m = re.search(r"Function Name: (\w+)", line)
     if m:
-      cur = res.setdefault(m.group(1), [])
+      cur = res.setdefault(symbol(m.group(1)), [])
       cur.append({})
       continue
     m = re.search(r"\s{3,}([A-Za-z][^:]*): (\S+) \[-Rpass", line)
@@ -87,6 +93,10 @@ def demangle(names):
       continue
     k = int(m.group(1))
     base, rest = n[m.end():m.end() + k], n[m.end() + k:]
+    m2 = re.match(r"(\d+)k_", rest)   # (a nested namespace, mcba::pnp::k_view_pose: the kernel's own name is the next component)
+    if m2:
+      k = int(m2.group(1))
+      base, rest = rest[m2.end(1):m2.end(1) + k], rest[m2.end(1) + k:]
     args = re.findall(r"L[ibjm](\d+)E", rest.split("EEv")[0]) if rest.startswith("I") else []
     out[n] = base + ("<" + ",".join(args) + ">" if args else "")
   return out
@@ -154,20 +164,27 @@ def main():
     return
   a_dir, a_log, b_dir, b_log = sys.argv[1:5]
   prefixes = sys.argv[5:]
-  ka, kb = kernels_of(a_dir), kernels_of(b_dir)
+  ua, ub = kernels_of(a_dir), kernels_of(b_dir)
+  ka, kb = set(ua), set(ub)
   print(f"kernel descriptors: A {len(ka)}, B {len(kb)}, only in A {len(ka - kb)}, only in B {len(kb - ka)}")
-  for unit, n in sorted(ka ^ kb):
-    print(f"  only in {'A' if (unit, n) in ka else 'B'}: {unit} {n}")
+  for n in sorted(ka ^ kb):
+    print(f"  only in {'A' if n in ka else 'B'}: {' '.join(sorted((ua if n in ka else ub)[n]))} {n}")
   la, lb = listings(a_dir), listings(b_dir)
   ra, rb = resources(a_log), resources(b_log)
-  names = demangle(sorted({n for _, n in ka | kb}))
+  names = demangle(sorted(ka | kb))
+  moved = sorted(n for n in ka & kb if sorted(ua[n]) != sorted(ub[n]))
+  print(f"kernels emitted by other translation units in B than in A: {len(moved)}")
+  for n in moved:
+    print(f"  {names[n]}: {' '.join(sorted(ua[n]))} -> {' '.join(sorted(ub[n]))}")
   print("kernel [unit] | " + " ".join(SHORT) + " (A, '-> B' where it differs) | instructions A B | differing lines: commuted inverted other")
   same = changed = 0
   fam = {}   # kernel family -> [instantiations, identical listing and figures]
-  for key in sorted(ka & kb, key=lambda k: (names[k[1]], k[0])):
-    unit, n = key
-    a, b = la.get(key, []), lb.get(key, [])
-    if a == b:
+  for n in sorted(ka & kb, key=lambda k: names[k]):
+    # (a symbol that several units emit has one listing per unit: compared as sets, the first of each printed)
+    sa, sb = sorted(set(map(tuple, la.get(n, {}).values()))), sorted(set(map(tuple, lb.get(n, {}).values())))
+    a, b = list(sa[0]) if sa else [], list(sb[0]) if sb else []
+    unit = " ".join(sorted(ub[n]))
+    if sa == sb:
       same += 1
     else:
       changed += 1
@@ -177,7 +194,7 @@ def main():
     fb = sorted({tuple(r.get(f, "?") for f in FIELDS) for r in rb.get(n, [{}])})
     f = fam.setdefault(names[n].split("<")[0], [0, 0])
     f[0] += 1
-    if a == b and fa == fb:   # identical kernels are only counted, per family below
+    if sa == sb and fa == fb:   # identical kernels are only counted, per family below
       f[1] += 1
       continue
     fig = " ".join(x if x == y else f"{x}->{y}" for x, y in zip(fa[0], fb[0])) if len(fa) == len(fb) == 1 else f"{fa} | {fb}"

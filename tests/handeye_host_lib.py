@@ -1,31 +1,18 @@
 """TEST INFRASTRUCTURE: ctypes wrapper of tests/handeye_host (g++ build of multical_amd/csrc/mcba_handeye.h, the mathematics of
 mcba_hand_eye) + the fixtures the hand-eye start tests share."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 from scipy.spatial.transform import Rotation
 
+import host_build
 from multical_amd import _lib, tables
 
 import pnp_host_lib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "handeye_host", "handeye_host.cpp")
-OUT_DIR = os.path.join(HERE, "handeye_host", "_build")
-LIB = os.path.join(OUT_DIR, "libmcba_handeye_host.so")
-
 
 def build(force=False):
-  os.makedirs(OUT_DIR, exist_ok=True)
-  root = os.path.dirname(HERE)
-  csrc = os.path.join(root, "multical_amd", "csrc")
-  deps = [SRC, os.path.join(root, "include", "mcba.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-  if force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-    # -ffp-contract=off: the host build is the plain IEEE evaluation of the formulas (the device contracts to FMAs)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", LIB, SRC])
-  return LIB
+  return host_build.build("handeye_host", "handeye_host.cpp", host_build.IEEE, force)
 
 
 _h = None
@@ -34,9 +21,9 @@ _h = None
 def lib():
   global _h
   if _h is None:
-    _h = C.CDLL(build())
+    build()
+    _h = host_build.load("handeye_host", "he")
     dp = C.POINTER(C.c_double)
-    _h.he_last_error.restype = C.c_char_p
     _h.he_hand_eye.restype = C.c_int32
     _h.he_hand_eye.argtypes = [C.POINTER(_lib.HandEyeProblem), dp, dp, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), dp, C.c_int32]
   return _h

@@ -1,26 +1,15 @@
 """TEST INFRASTRUCTURE: ctypes wrapper of tests/hostmath (g++ build of the product's __host__ __device__ functions)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import host_build
 from multical_amd import _lib
 from multical_amd.backend import lower, _to_struct, _ptr, _f64
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "hostmath", "hostmath.cpp")
-OUT_DIR = os.path.join(HERE, "hostmath", "_build")
-LIB = os.path.join(OUT_DIR, "libmcba_hostmath.so")
-
 
 def build(force=False):
-  os.makedirs(OUT_DIR, exist_ok=True)
-  csrc = os.path.join(os.path.dirname(HERE), "multical_amd", "csrc")
-  deps = [SRC] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-  if force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-o", LIB, SRC])
-  return LIB
+  return host_build.build("hostmath", "hostmath.cpp", ["-pthread"], force)
 
 
 _h = None
@@ -29,8 +18,8 @@ _h = None
 def lib():
   global _h
   if _h is None:
-    _h = C.CDLL(build())
-    _h.hm_last_error.restype = C.c_char_p
+    build()
+    _h = host_build.load("hostmath", "hm")
   return _h
 
 

@@ -1,29 +1,16 @@
 """TEST INFRASTRUCTURE: ctypes wrapper of tests/intrinsic_host (g++ build of multical_amd/csrc/mcba_intrinsic.h, the mathematics of
 mcba_calibrate_intrinsics) behind tables.calibrate_intrinsics' signature, + the rigs the intrinsic tests share."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import host_build
 from multical_amd import _lib, synthetic, tables
 from multical_amd.structs import struct
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "intrinsic_host", "intrinsic_host.cpp")
-OUT_DIR = os.path.join(HERE, "intrinsic_host", "_build")
-LIB = os.path.join(OUT_DIR, "libmcba_intrinsic_host.so")
-
 
 def build(force=False):
-  os.makedirs(OUT_DIR, exist_ok=True)
-  root = os.path.dirname(HERE)
-  csrc = os.path.join(root, "multical_amd", "csrc")
-  deps = [SRC, os.path.join(root, "include", "mcba.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-  if force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-    # -ffp-contract=off: the host build is the plain IEEE evaluation of the formulas (the device contracts to FMAs)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", LIB, SRC])
-  return LIB
+  return host_build.build("intrinsic_host", "intrinsic_host.cpp", host_build.IEEE, force)
 
 
 _h = None
@@ -32,9 +19,9 @@ _h = None
 def lib():
   global _h
   if _h is None:
-    _h = C.CDLL(build())
+    build()
+    _h = host_build.load("intrinsic_host", "intrinsic")
     dp, up, ip = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
-    _h.intrinsic_last_error.restype = C.c_char_p
     _h.intrinsic_calibrate.restype = C.c_int32
     _h.intrinsic_calibrate.argtypes = [C.POINTER(_lib.IntrinsicProblem), dp, dp, dp, ip, up, up, C.c_int32]
   return _h

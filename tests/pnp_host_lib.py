@@ -2,27 +2,17 @@
 mathematics of mcba_view_poses) + the fixtures the pose-table tests share."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import host_build
 from multical_amd import _lib, synthetic, tables
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "pnp_host", "pnp_host.cpp")
-OUT_DIR = os.path.join(HERE, "pnp_host", "_build")
-LIB = os.path.join(OUT_DIR, "libmcba_pnp_host.so")
+HERE = host_build.HERE
 
 
 def build(force=False):
-  os.makedirs(OUT_DIR, exist_ok=True)
-  root = os.path.dirname(HERE)
-  csrc = os.path.join(root, "multical_amd", "csrc")
-  deps = [SRC, os.path.join(root, "include", "mcba.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
-  if force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-    # -ffp-contract=off: the host build is the plain IEEE evaluation of the formulas (the device contracts to FMAs)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", LIB, SRC])
-  return LIB
+  return host_build.build("pnp_host", "pnp_host.cpp", host_build.IEEE, force)
 
 
 _h = None
@@ -31,8 +21,8 @@ _h = None
 def lib():
   global _h
   if _h is None:
-    _h = C.CDLL(build())
-    _h.pnp_last_error.restype = C.c_char_p
+    build()
+    _h = host_build.load("pnp_host", "pnp")
     _h.pnp_view_poses.restype = C.c_int32
     _h.pnp_view_poses.argtypes = [C.POINTER(_lib.ViewPoseProblem), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int32]

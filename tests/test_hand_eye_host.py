@@ -267,3 +267,13 @@ def test_hand_eye_robot_world_and_its_transposed_form():
   assert np.abs(bw_t - np.linalg.inv(X)).max() <= 1e-11 and np.abs(gc_t - np.linalg.inv(Z)).max() <= 1e-11
   with pytest.raises(ValueError, match="fewer than 3"):
     hand_eye.hand_eye_robot_world(A[:2], B[:2], solver=hh.hand_eye_batch)
+
+
+def test_library_reports_a_refusal_thrown_in_the_hand_eye_unit():
+  """No device needed: the argument check of mcba_hand_eye throws in its own translation unit (csrc/mcba_handeye.hip) and
+  mcba_last_error(), defined in another one, carries the message -- the host runtime's objects exist once per library."""
+  from multical_amd import _lib
+  ta, va, tb, vb, _, _ = hh.interleaved_problem(5, 6, n_rows=2)
+  with pytest.raises(_lib.McbaError, match=r"mcba_hand_eye: problem 1: rows \(2, 1\) outside tables of 2 and 2 rows"):
+    tables.hand_eye_batch(ta, va, tb, vb, [0, 2], [0, 1])
+  assert "rows (2, 1)" in _lib.load().mcba_last_error().decode()

@@ -1,38 +1,21 @@
 """TEST INFRASTRUCTURE: ctypes wrapper of tests/undistort_host (g++ build of multical_amd/csrc/mcba_undistort.h, the mathematics of
 the undistortion entry points) + the fixtures the undistortion tests share."""
 import contextlib
-import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import host_build
 from multical_amd import _lib, undistort
 from multical_amd.camera import Camera, CameraFisheye
 
 import pnp_host_lib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "undistort_host", "undistort_host.cpp")
-OUT_DIR = os.path.join(HERE, "undistort_host", "_build")
-LIB = os.path.join(OUT_DIR, "libmcba_undistort_host.so")
+HERE = host_build.HERE
 NAMES = ["project_points", "undistort_points", "undistort_maps", "remap", "undistort_images"]
-# -ffp-contract=off: the host build is the plain IEEE evaluation of the formulas (the device contracts FP64 expressions to FMAs;
-# the float32 interpolation is written in explicit fmaf and must not change with this flag)
-FLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off"]
-
-
-def sources():
-  root = os.path.dirname(HERE)
-  csrc = os.path.join(root, "multical_amd", "csrc")
-  return [SRC, os.path.join(root, "include", "mcba.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
 
 
 def build(force=False):
-  os.makedirs(OUT_DIR, exist_ok=True)
-  if force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in sources()):
-    subprocess.check_call(["g++"] + FLAGS + ["-shared", "-o", LIB, SRC])
-  return LIB
+  return host_build.build("undistort_host", "undistort_host.cpp", host_build.IEEE, force)
 
 
 _h = None
@@ -41,8 +24,8 @@ _h = None
 def lib():
   global _h
   if _h is None:
-    _h = C.CDLL(build())
-    _h.uh_last_error.restype = C.c_char_p
+    build()
+    _h = host_build.load("undistort_host", "uh")
     signatures = {name: (restype, argtypes) for name, restype, argtypes in _lib.SYMBOLS}
     for name in NAMES:
       fn = getattr(_h, "uh_" + name)
