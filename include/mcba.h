@@ -517,6 +517,39 @@ int32_t mcba_undistort_images(const mcba_camera_set* cams, const double* R, cons
                               int32_t Hs, int32_t Ws, int32_t channels, int32_t dtype, const int32_t* camera_of_image, int32_t Hd,
                               int32_t Wd, double border, void* dst);
 
+/* --- using a calibration: triangulate points through the rig --------------------------------------------------------- */
+/* The 3-D point behind the pixels that the cameras of a calibrated rig saw at once, for F frames of M points each in one launch
+ * (csrc/mcba_triangulate.h: exact undistortion, plane-intersection start, Levenberg-Marquardt on the pixel residuals of the
+ * project's own projection to a whitened step of 1e-10 px).  A view is a (camera, frame) pair with the row-major 3 x 4 matrix that
+ * takes a point into the camera frame: the top three rows of camera_pose[c] @ rig_pose[f].  Rolling shutter: an observation at row
+ * v sees (1 - t) views + t views_end, t = v / image_heights[c].  Handle-less like mcba_view_poses; same error convention, the
+ * caller owns every array.  The records of a frame are staged in LDS: more than MCBA_TRI_MAX_CAMERAS cameras are refused.        */
+#define MCBA_TRI_MAX_CAMERAS 64
+#define MCBA_TRI_OK 0              /* converged                                                                          */
+#define MCBA_TRI_TOO_FEW 1         /* fewer than 2 usable views (valid, finite, inside the model's monotone range): no point  */
+#define MCBA_TRI_DEGENERATE 2      /* the rays are parallel or one and the same: no point                                 */
+#define MCBA_TRI_NOT_CONVERGED 3   /* max_iterations linearisations did not meet the stop rule: the last iterate         */
+#define MCBA_TRI_BEHIND 4          /* the returned point lies at or behind the plane of a view that entered              */
+typedef struct mcba_triangulate_problem {
+  mcba_camera_set cams;          /* C cameras */
+  int32_t F; int64_t M;          /* frames, points per frame */
+  const double* views;           /* [C,F,3,4] */
+  const double* views_end;       /* [C,F,3,4] or NULL (no rolling shutter) */
+  const double* image_heights;   /* [C], required with views_end */
+  const uint8_t* view_valid;     /* [C,F] or NULL */
+  const double* points;          /* [C,F,M,2] pixels */
+  const uint8_t* valid;          /* [C,F,M] */
+  double sigma_px; int32_t max_iterations;   /* sigma_px <= 0: sse / (2 n - 3) per point; max_iterations <= 0: 20, at most 100 */
+} mcba_triangulate_problem;
+/* Outputs: X [F,M,3]; cov [F,M,6] upper triangle (xx xy xz yy yz zz) of sigma^2 (J^T J)^-1 at X; sse [F,M] squared pixel residuals;
+ * err [C,F,M] reprojection error of every view that entered, 0 elsewhere; n_views [F,M] usable views; status [F,M] MCBA_TRI_*.
+ * Points without a result: NaN in X and cov, sse 0.  cov, sse, err and n_views may be NULL.  F * M == 0 launches nothing.       */
+int32_t mcba_triangulate(const mcba_triangulate_problem* p, double* X, double* cov, double* sse, double* err, int32_t* n_views,
+                         uint8_t* status);
+/* timing of the last mcba_triangulate call of this thread, milliseconds: [0] uploads, [1] kernel (HIP events around the launch),
+ * [2] downloads, [3] the whole call; *n_points (or NULL) = points launched                                                 */
+int32_t mcba_debug_triangulate_ms(double* ms /*[4]*/, int64_t* n_points);
+
 /* --- solve -------------------------------------------------------------------------------------------------- */
 /* Trust-region least squares: replaces scipy.optimize.least_squares(method='trf', x_scale='jac', jac_sparsity=S,
  * loss, f_scale, ftol, max_nfev) at calibration.py:209-210.  x is updated in place to `res.x`.                 */

@@ -82,6 +82,14 @@ class CameraSet(C.Structure):   # mcba_camera_set
               ("is_fisheye", c_uint8_p)]
 
 
+class TriangulateProblem(C.Structure):   # mcba_triangulate_problem
+  _fields_ = [("cams", CameraSet), ("F", C.c_int32), ("M", C.c_int64), ("views", c_double_p), ("views_end", c_double_p),
+              ("image_heights", c_double_p), ("view_valid", c_uint8_p), ("points", c_double_p), ("valid", c_uint8_p),
+              ("sigma_px", C.c_double), ("max_iterations", C.c_int32)]
+
+
+TRI_OK, TRI_TOO_FEW, TRI_DEGENERATE, TRI_NOT_CONVERGED, TRI_BEHIND = 0, 1, 2, 3, 4   # MCBA_TRI_*
+TRI_MAX_CAMERAS = 64                                  # MCBA_TRI_MAX_CAMERAS
 PIXEL_U8, PIXEL_F32 = 0, 1                            # MCBA_PIXEL_*
 UNDISTORT_OK, UNDISTORT_NOT_CONVERGED = 0, 1          # MCBA_UNDISTORT_*
 
@@ -131,6 +139,9 @@ SYMBOLS = [
   ("mcba_undistort_images", C.c_int32, [C.POINTER(CameraSet), c_double_p, c_double_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p]),
   ("mcba_debug_undistort_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_triangulate", C.c_int32, [C.POINTER(TriangulateProblem), c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
+                                   c_uint8_p]),
+  ("mcba_debug_triangulate_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_error_stats", C.c_int32, [H, c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), c_double_p,
                                    C.POINTER(C.c_int64), c_double_p]),
   ("mcba_error_count", C.c_int32, [H, C.c_int32, C.POINTER(C.c_int64)]),

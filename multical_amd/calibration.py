@@ -626,6 +626,70 @@ class Calibration(parameters.Parameters):
            f"max leverage={float(l.max()) if l.size else float('nan'):.4f}")
 
 
+  # --- triangulation through the rig --------------------------------------------------------------
+  @cached_property
+  def world_points(self):
+    """calibration.py:83-90: board points in the rig's world frame, board_pose[b] . X_board: Table(points [B, P, 3], valid [B, P])."""
+    B, P = self.size.boards, self.size.points
+    pts, valid = np.zeros((B, P, 3)), np.zeros((B, P), dtype=bool)
+    for b, board in enumerate(self.boards):
+      x = np.asarray(board.adjusted_points, dtype=np.float64)
+      pts[b, :len(x)] = x
+      valid[b, :len(x)] = True
+    poses = np.asarray(self.board_poses.poses, dtype=np.float64)
+    world = np.einsum('bij,bpj->bpi', poses[:, :3, :3], pts) + poses[:, None, :3, 3]
+    return Table.create(points=world, valid=valid & np.asarray(self.board_poses.valid)[:, None])
+
+  def _rig_poses(self):
+    """(start [F, 4, 4], end [F, 4, 4] or None) of the motion model: static, rolling shutter, hand-eye through its pose table"""
+    m = self.motion
+    if hasattr(m, "pose_start"):
+      return np.asarray(m.pose_start), np.asarray(m.pose_end)
+    return np.asarray(m.frame_poses.poses), None
+
+  def triangulate(self, inliers_only=True, sigma=None, max_iterations=20):
+    """Every corner of the point table intersected from the cameras that saw it in its frame (multical_amd.triangulate, one launch,
+    M = B * P): Table(points [F, B, P, 3], valid [F, B, P], n_views, cov [F, B, P, 3, 3], status, error [C, F, B, P]) in the frame
+    of `world_points`.  The mask is `inliers` (inliers_only) or `valid`; a corner is valid where the triangulation converged, which
+    takes two cameras at least."""
+    from . import triangulate as tri
+    C, F, B, P = self.point_table.valid.shape
+    mask = self.inliers if inliers_only else self.valid
+    start, end = self._rig_poses()
+    view_valid = np.asarray(self.camera_poses.valid)[:, None] & np.asarray(self.motion.valid)[None, :]
+    r = tri.triangulate_rig(self.cameras, self.camera_poses.poses, start, np.asarray(self.point_table.points).reshape(C, F, B * P, 2),
+                            np.asarray(mask).reshape(C, F, B * P), rig_poses_end=end, view_valid=view_valid, sigma=sigma,
+                            max_iterations=max_iterations)
+    return Table.create(points=r.points.reshape(F, B, P, 3), valid=(r.status == tri.OK).reshape(F, B, P),
+                        n_views=r.n_views.reshape(F, B, P), cov=r.cov.reshape(F, B, P, 3, 3), status=r.status.reshape(F, B, P),
+                        error=r.error.reshape(C, F, B, P))
+
+  def reconstruction_error(self, inliers_only=True):
+    """How good the calibration is in the units of the boards: the distance of every triangulated corner from where the rig chain
+    puts it (world_points[b, p]).  struct(error [F, B, P] (0 where invalid), valid, n_views, overall, boards): `overall` and
+    boards[b] are error_stats of the valid corners (mse, rms, quantiles 0 .25 .5 .75 1, n)."""
+    t = self.triangulate(inliers_only=inliers_only)
+    world = self.world_points
+    valid = t.valid & world.valid[None]
+    with np.errstate(invalid="ignore"):
+      dist = np.linalg.norm(t.points - world.points[None], axis=-1)
+    dist = np.where(valid, dist, 0.0)
+    boards = [error_stats(dist[:, b][valid[:, b]]) for b in range(self.size.boards)]
+    return struct(error=dist, valid=valid, n_views=t.n_views, overall=error_stats(dist[valid]), boards=boards)
+
+  def report_reconstruction(self, stage="", inliers_only=True):
+    """One line through the "calibration" logger: RMS, median and largest 3-D distance between triangulated and predicted corners in
+    millimetres (boards in metres), and how many corners two cameras or more saw."""
+    r = self.reconstruction_error(inliers_only=inliers_only)
+    n = int(r.valid.sum())
+    if n == 0:
+      info(f"{stage} reconstruction: no corner was seen by 2 or more cameras")
+      return
+    q = r.overall.quantiles
+    info(f"{stage} reconstruction RMS={1e3 * r.overall.rms:.3f} mm, median={1e3 * q[2]:.3f} mm, max={1e3 * q[4]:.3f} mm, "
+         f"n={n} corners seen by >= 2 cameras")
+
+
 def split_std(calib, std):
   """A vector over calib.param_vec (standard deviations) split into the enabled blocks: camera_poses [C, 6], board_poses
   [B, 6], motion (static [F, 6]; rolling shutter [start [F, 6], end [F, 6]]; hand-eye struct(world_wrt_base [6],
