@@ -645,7 +645,9 @@ class Handle(object):
     check(self.lib.mcba_debug_set_allreduce_trace(self.h, int(cap)))
 
   def set_lsmr_grid(self, grid):
-    """persistent workgroups of the LSMR product kernels (default 2048): only the summation order changes -- experiment hook"""
+    """persistent workgroups of the LSMR product kernels (default 2048, any number >= 1; never more than the rig has views): above the
+    number of views only the summation order changes, below it a workgroup walks several views in turn (1: one wavefront walks them
+    all) -- experiment / test hook"""
     check(self.lib.mcba_debug_set_lsmr_grid(self.h, int(grid)))
 
   def lsmr_iterations(self):

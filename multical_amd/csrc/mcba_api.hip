@@ -2388,7 +2388,7 @@ static void solve_lsmr(mcba_handle h, double* x_inout, const mcba_options* opt, 
   const double NaN = std::numeric_limits<double>::quiet_NaN();
   double* S = h->h_scal;
   // (persistent single-wave workgroups of the product kernels: h->lsmr_grid, default 2048; MCBA_LSMR_GRID: process-wide debug switch)
-  if (const char* gsw = dbg_switch("MCBA_LSMR_GRID")) h->lsmr_grid = std::max(64, atoi(gsw));
+  if (const char* gsw = dbg_switch("MCBA_LSMR_GRID")) h->lsmr_grid = std::max(1, std::min(65536, atoi(gsw)));   // (mcba_debug_set_lsmr_grid's range)
   LsmrOps op = lsmr_setup(h);
   const size_t m = op.m;
   h->lsmr_trace.clear();
@@ -2711,11 +2711,13 @@ int32_t mcba_debug_set_allreduce_trace(mcba_handle h, int32_t cap) {
   API_END
 }
 
-/* persistent single-wave workgroups of the LSMR product kernels on this handle (default 2048; >= 64): changes only the order in
- * which partial sums are folded -- the summation-order experiment of profiles/r06_lsmr_sign.* */
+/* persistent single-wave workgroups of the LSMR product kernels on this handle (default 2048; never more than the rig has views):
+ * changes only the order in which partial sums are folded -- the summation-order experiment of profiles/r06_lsmr_sign.* -- and, below
+ * the number of views, makes a workgroup walk several views in turn (grid 1: ONE wavefront walks them all; tests/test_gpu_view_edges.py).
+ * Every product kernel strides its views and its slice of the vector update by the grid, so any grid >= 1 is valid. */
 int32_t mcba_debug_set_lsmr_grid(mcba_handle h, int32_t grid) {
   API_BEGIN
-  REQUIRE(h && grid >= 64 && grid <= 65536, "bad grid");
+  REQUIRE(h && grid >= 1 && grid <= 65536, "bad grid");
   h->lsmr_grid = grid;
   API_END
 }

@@ -68,7 +68,7 @@ int32_t mcba_debug_set_lsmr_trace(mcba_handle h, int32_t scalars);
 int32_t mcba_debug_set_lsmr_masks_form(mcba_handle h, int32_t on);
 /* number of collective sizes mcba_allreduce_stats records per handle (default 4096; a whole sharded lsmr solve issues more)       */
 int32_t mcba_debug_set_allreduce_trace(mcba_handle h, int32_t cap);
-/* persistent workgroups of the LSMR product kernels (default 2048): summation-order experiments                                 */
+/* persistent workgroups of the LSMR product kernels (default 2048, >= 1): summation-order experiments, several views per workgroup */
 int32_t mcba_debug_set_lsmr_grid(mcba_handle h, int32_t grid);
 /* HIP-event time (ms) of the per-observation pass alone (k_obscov + k_obscov_fold) in the last mcba_observation_covariance      */
 int32_t mcba_debug_observation_covariance_ms(mcba_handle h, double* ms);

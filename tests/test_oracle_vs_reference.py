@@ -8,10 +8,25 @@ from oracle import restate
 pytestmark = pytest.mark.needs_reference
 
 
-@pytest.mark.parametrize("name", ["tiny", "tiny_rolling", "tiny_fisheye", "tiny_handeye", "tiny_tilted"])
+def _planted_names():
+  import planted_rigs as pr
+  return ({"edges-" + pr.shape_id(s): (pr.planted_rig, s) for s in pr.SHAPES} |
+          {"bigboard-" + pr.shape_id(s): (pr.planted_bigboard, s) for s in pr.BIG_SHAPES})
+
+
+PLANTED = _planted_names()
+
+
+@pytest.mark.parametrize("name", ["tiny", "tiny_rolling", "tiny_fisheye", "tiny_handeye", "tiny_tilted"] + list(PLANTED))
 def test_restatement_is_bit_identical_to_reference(name):
+  """... and on the planted rigs of tests/planted_rigs.py: all 42 camera x motion x intrinsics shapes with their views cut to the
+  chunk-edge counts, and the three rigs with an 816-point board."""
   from oracle import build_reference
-  rig = synthetic.make_rig(name)
+  if name in PLANTED:
+    make, shape = PLANTED[name]
+    rig = make(*shape)[0]
+  else:
+    rig = synthetic.make_rig(name)
   ref_calib, ref = build_reference.reference_calibration(rig)
   oc = restate.from_rig(rig)
   x = ref_calib.param_vec
