@@ -550,6 +550,48 @@ int32_t mcba_triangulate(const mcba_triangulate_problem* p, double* X, double* c
  * [2] downloads, [3] the whole call; *n_points (or NULL) = points launched                                                 */
 int32_t mcba_debug_triangulate_ms(double* ms /*[4]*/, int64_t* n_points);
 
+/* --- using a calibration: localise the rig in frames that were not part of it (multi-camera PnP) ---------------------- */
+/* The dual of mcba_triangulate: cameras, camera poses, boards and board poses are held, and the rig pose of each of F frames is
+ * found from that frame's detections alone (csrc/mcba_localize.h: one workgroup per frame, Levenberg-Marquardt on the pixel
+ * residuals of the project's own projection over the global rotation vector and the translation of the frame's pose -- start, then
+ * end under rolling shutter, t = v / image_heights[c] -- to a whitened step of 1e-10 px).  An observation is usable where valid and
+ * board_valid say so and the pixel is finite.  Without `init` a frame starts from the best of up to four candidates
+ * camera_pose[c]^-1 T_view board_pose[b]^-1 of its largest views (the mathematics of mcba_view_poses; status OK, most corners first),
+ * scored over all its observations; a frame none of whose views gives a pose has no start.  Handle-less like mcba_view_poses; same
+ * error convention, the caller owns every array.  More than MCBA_RIG_MAX_CAMERAS cameras are refused.                            */
+#define MCBA_RIG_MAX_CAMERAS 64
+#define MCBA_RIG_OK 0              /* converged                                                                          */
+#define MCBA_RIG_TOO_FEW 1         /* fewer than 3 usable observations (6 under rolling shutter): no pose                 */
+#define MCBA_RIG_DEGENERATE 2      /* a vanishing pivot of the scaled normal matrix (collinear points), a cost that is not  */
+                                   /* finite, or no start: no pose                                                        */
+#define MCBA_RIG_NOT_CONVERGED 3   /* max_iterations linearisations did not meet the stop rule: the last iterate         */
+#define MCBA_RIG_BEHIND 4          /* an observation that entered ends at or behind its camera                            */
+typedef struct mcba_rig_pose_problem {
+  mcba_camera_set cams;          /* C cameras */
+  int32_t F, B, P;               /* frames, boards, padded corners per board */
+  const double* camera_poses;    /* [C,4,4] rig -> camera */
+  const double* board_poses;     /* [B,4,4] board -> world */
+  const double* board_points;    /* [B,P,3] board geometry, padded at the end of a row */
+  const uint8_t* board_valid;    /* [B,P] or NULL = every point; holes allowed (a masked point enters nothing, the start's plane fit included) */
+  const double* points;          /* [C,F,B,P,2] pixels */
+  const uint8_t* valid;          /* [C,F,B,P] */
+  const double* init;            /* [F,4,4] start poses world -> rig, or NULL = from the frame's views */
+  const double* init_end;        /* [F,4,4] start of the end poses (rolling), or NULL = init */
+  int32_t rolling;               /* != 0: 12 unknowns a frame */
+  const double* image_heights;   /* [C], required with rolling */
+  double sigma_px; int32_t max_iterations;   /* sigma_px <= 0: the frame's own sse / (2 n - k); max_iterations <= 0: 20, at most 100 */
+} mcba_rig_pose_problem;
+/* Outputs: poses [F,4,4]; poses_end [F,4,4] (rolling; identity otherwise); cov [F,21] or [F,78] upper triangle by rows of
+ * sigma^2 (J^T J)^-1 over (rx ry rz tx ty tz) of the start, then of the end; sse [F]; n_obs [F] usable observations; iters [F]
+ * linearisations; err [C,F,B,P] reprojection error of every observation that entered, 0 elsewhere; status [F] MCBA_RIG_*.  Frames
+ * without a result: identity, sse 0, NaN in cov (also where sigma_px <= 0 and 2 n = k).  Every output but poses and status may be
+ * NULL.  F == 0 or a table without a usable observation launches nothing.                                                  */
+int32_t mcba_rig_poses(const mcba_rig_pose_problem* p, double* poses, double* poses_end, double* cov, double* sse, int32_t* n_obs,
+                       int32_t* iters, double* err, uint8_t* status);
+/* timing of the last mcba_rig_poses call of this thread, milliseconds: [0] uploads, [1] start kernel (k_view_pose; 0 with init),
+ * [2] refinement kernel (both by HIP events), [3] downloads, [4] the whole call; *n_frames (or NULL) = frames launched       */
+int32_t mcba_debug_rig_poses_ms(double* ms /*[5]*/, int64_t* n_frames);
+
 /* --- solve -------------------------------------------------------------------------------------------------- */
 /* Trust-region least squares: replaces scipy.optimize.least_squares(method='trf', x_scale='jac', jac_sparsity=S,
  * loss, f_scale, ftol, max_nfev) at calibration.py:209-210.  x is updated in place to `res.x`.                 */

@@ -88,8 +88,17 @@ class TriangulateProblem(C.Structure):   # mcba_triangulate_problem
               ("sigma_px", C.c_double), ("max_iterations", C.c_int32)]
 
 
+class RigPoseProblem(C.Structure):   # mcba_rig_pose_problem
+  _fields_ = [("cams", CameraSet), ("F", C.c_int32), ("B", C.c_int32), ("P", C.c_int32), ("camera_poses", c_double_p),
+              ("board_poses", c_double_p), ("board_points", c_double_p), ("board_valid", c_uint8_p), ("points", c_double_p),
+              ("valid", c_uint8_p), ("init", c_double_p), ("init_end", c_double_p), ("rolling", C.c_int32),
+              ("image_heights", c_double_p), ("sigma_px", C.c_double), ("max_iterations", C.c_int32)]
+
+
 TRI_OK, TRI_TOO_FEW, TRI_DEGENERATE, TRI_NOT_CONVERGED, TRI_BEHIND = 0, 1, 2, 3, 4   # MCBA_TRI_*
 TRI_MAX_CAMERAS = 64                                  # MCBA_TRI_MAX_CAMERAS
+RIG_OK, RIG_TOO_FEW, RIG_DEGENERATE, RIG_NOT_CONVERGED, RIG_BEHIND = 0, 1, 2, 3, 4   # MCBA_RIG_*
+RIG_MAX_CAMERAS = 64                                  # MCBA_RIG_MAX_CAMERAS
 PIXEL_U8, PIXEL_F32 = 0, 1                            # MCBA_PIXEL_*
 UNDISTORT_OK, UNDISTORT_NOT_CONVERGED = 0, 1          # MCBA_UNDISTORT_*
 
@@ -142,6 +151,9 @@ SYMBOLS = [
   ("mcba_triangulate", C.c_int32, [C.POINTER(TriangulateProblem), c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
                                    c_uint8_p]),
   ("mcba_debug_triangulate_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_rig_poses", C.c_int32, [C.POINTER(RigPoseProblem), c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p,
+                                 c_double_p, c_uint8_p]),
+  ("mcba_debug_rig_poses_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_error_stats", C.c_int32, [H, c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), c_double_p,
                                    C.POINTER(C.c_int64), c_double_p]),
   ("mcba_error_count", C.c_int32, [H, C.c_int32, C.POINTER(C.c_int64)]),

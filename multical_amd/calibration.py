@@ -690,6 +690,61 @@ class Calibration(parameters.Parameters):
          f"n={n} corners seen by >= 2 cameras")
 
 
+  # --- localising the rig in other frames ---------------------------------------------------------
+  def localize(self, point_table=None, inliers_only=True, init=None, sigma=None, max_iterations=20):
+    """The rig pose of every frame of `point_table` from that frame's detections alone, cameras, camera poses, boards and board
+    poses held (multical_amd.localize, one workgroup per frame).  Default table: the calibration's own, over its inliers
+    (inliers_only) or valid points, started from the current poses of the motion model.  Another table is started from its own views
+    unless init ([F, 4, 4], or (start, end) under rolling shutter) is given.  A RollingFrames motion gives start and end poses; a
+    HandEye motion is localised as static frames.  Returns the struct of localize.localize_rig."""
+    from . import localize as loc
+    own = point_table is None
+    table = self.point_table if own else point_table
+    rolling = hasattr(self.motion, "pose_start")
+    shared = np.asarray(self.camera_poses.valid)[:, None, None, None] & np.asarray(self.board_poses.valid)[None, None, :, None]
+    mask = (self.inliers if inliers_only else self.valid) if own else (np.asarray(table.valid) & shared)
+    start, end = (None, None)
+    if init is not None:
+      start, end = init if isinstance(init, (tuple, list)) else (init, None)
+    elif own:
+      start, end = self._rig_poses()
+    return loc.localize_rig(self.cameras, self.camera_poses.poses, self.board_poses.poses,
+                            [np.asarray(b.adjusted_points, dtype=np.float64) for b in self.boards], table.points, mask, init=start,
+                            init_end=end if rolling else None, rolling=rolling, sigma=sigma, max_iterations=max_iterations)
+
+  def with_localized_frames(self, point_table, names=None):
+    """A new Calibration with the same cameras, camera poses, boards and board poses over the frames of `point_table`: the motion is
+    StaticFrames / RollingFrames of the localised poses, valid where the localisation converged (a HandEye calibration yields
+    StaticFrames).  report(), reprojection_error, reject_outliers, reconstruction_error() and bundle_adjust then work on the held-out
+    table unchanged."""
+    from . import localize as loc
+    from .motion import RollingFrames, StaticFrames
+    r = self.localize(point_table)
+    ok = r.status == loc.OK
+    names = list(names) if names is not None else [str(i) for i in range(len(ok))]
+    if r.poses_end is not None:
+      motion = RollingFrames(r.poses, r.poses_end, ok, names, getattr(self.motion, "max_iterations", 4))
+    else:
+      motion = StaticFrames(Table.create(poses=r.poses, valid=ok), names)
+    return self.copy(point_table=point_table, motion=motion, inlier_mask=None)
+
+  def report_holdout(self, point_table, stage=""):
+    """One line through the "calibration" logger: frames localised / total, RMS and quantiles of the held-out reprojection error
+    (pixels, over the observations of the localised frames) and the median standard deviation of the frames' translations (board
+    units, sqrt of the trace of the translation block of each frame's covariance)."""
+    from . import localize as loc
+    r = self.localize(point_table)
+    ok = r.status == loc.OK
+    entered = (r.error > 0) & ok[None, :, None, None]
+    stats = error_stats(r.error[entered])
+    with np.errstate(invalid="ignore"):
+      t_std = np.sqrt(np.trace(r.cov[:, 3:6, 3:6], axis1=1, axis2=2))[ok]
+    med = float(np.median(t_std)) if t_std.size else float("nan")
+    info(f"{stage} held-out: {int(ok.sum())} / {len(ok)} frames localised, reprojection RMS={stats.rms:.3f}, n={stats.n}, "
+         f"quantiles={stats.quantiles}, median translation std={med:.6f}")
+    return r
+
+
 def split_std(calib, std):
   """A vector over calib.param_vec (standard deviations) split into the enabled blocks: camera_poses [C, 6], board_poses
   [B, 6], motion (static [F, 6]; rolling shutter [start [F, 6], end [F, 6]]; hand-eye struct(world_wrt_base [6],

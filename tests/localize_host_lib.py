@@ -1,0 +1,256 @@
+"""TEST INFRASTRUCTURE: ctypes wrapper of tests/localize_host (g++ build of multical_amd/csrc/mcba_localize.h, the mathematics of
+mcba_rig_poses) + the rigs the localisation tests share.
+
+The rigs come from multical_amd.synthetic.make_rig with a configuration of their own (cameras x boards x camera model x motion), at
+the TRUTH calibration: localisation holds everything but the frames' poses, so a noise-free table has its optimum at the truth.
+"""
+import contextlib
+import ctypes as C
+from types import SimpleNamespace
+
+import numpy as np
+
+import host_build
+from multical_amd import _lib, localize, synthetic
+
+HERE = host_build.HERE
+NOISE_PX = 0.2
+
+# name: cameras, boards, camera model(s), rolling
+RIGS = {
+  "1cam-1board-pin5": (1, 1, "standard", False),
+  "2cam-2board-rational": (2, 2, "rational", False),
+  "8cam-2board-pin5": (8, 2, "standard", False),
+  "2cam-1board-fisheye": (2, 1, "fisheye", False),
+  "4cam-2board-mixed": (4, 2, ["standard", "fisheye", "rational", "pin4"], False),
+  # (one camera and ONE board under rolling shutter is left out: start and end pose from the few image rows a single small board
+  #  covers is conditioned 1e9, and the loop does not meet its stop rule there within 100 linearisations: DESIGN 3.13)
+  "1cam-2board-pin5-rolling": (1, 2, "standard", True),
+  "2cam-2board-mixed-rolling": (2, 2, ["pin4", "fisheye"], True),
+  "8cam-1board-rational-rolling": (8, 1, "rational", True),
+}
+RIG_IDS = list(RIGS)
+
+
+def build(force=False):
+  return host_build.build("localize_host", "localize_host.cpp", host_build.IEEE, force)
+
+
+_h = None
+
+
+def lib():
+  global _h
+  if _h is None:
+    build()
+    _h = host_build.load("localize_host", "lh")
+    signatures = {name: (restype, argtypes) for name, restype, argtypes in _lib.SYMBOLS}
+    _h.lh_rig_poses.restype, _h.lh_rig_poses.argtypes = signatures["mcba_rig_poses"]
+    dp = C.POINTER(C.c_double)
+    _h.lh_score_candidates.restype = C.c_int32
+    _h.lh_score_candidates.argtypes = [C.POINTER(_lib.RigPoseProblem), C.c_int32, C.c_int32, dp, dp, C.POINTER(C.c_int32)]
+  return _h
+
+
+def entry(name):
+  """localize._entry of the host build"""
+  fn = getattr(lib(), "lh_" + name)
+
+  def call(*args):
+    if fn(*args) != 0:
+      raise RuntimeError(lib().lh_last_error().decode())
+  return call
+
+
+@contextlib.contextmanager
+def host_backend():
+  """multical_amd.localize (and what sits on it: Calibration.localize, with_localized_frames) served by the host build"""
+  saved = localize._entry
+  localize._entry = entry
+  try:
+    yield localize
+  finally:
+    localize._entry = saved
+
+
+def on_host(fn, *args, **kwargs):
+  with host_backend():
+    return fn(*args, **kwargs)
+
+
+# ---- rigs ------------------------------------------------------------------------------------------------------------------
+_rigs = {}
+
+
+def make_rig(cameras, boards, model, rolling, frames=4, seed=101, noise=NOISE_PX):
+  """struct of one synthetic call at the truth calibration: cameras, camera_poses, board_poses, board_points (list), points
+  [C,F,B,P,2], valid, rig_poses (truth), rig_poses_end, rolling.  Cached: the tests share it and leave it unchanged."""
+  key = (cameras, boards, str(model), rolling, frames, seed, noise)
+  if key in _rigs:
+    return _rigs[key]
+  cfg = dict(cameras=cameras, frames=frames, boards=["charuco_10x10"] * boards, motion="rolling" if rolling else "static", model=model,
+             optimize_cameras=False, layout="stereo", seed=seed)
+  r = synthetic.make_rig(cfg, noise=noise, outlier_frac=0.0)
+  t = r.truth
+  out = SimpleNamespace(cameras=t.cameras, camera_poses=t.camera_poses, board_poses=t.board_poses, board_points=list(r.board_points),
+                        points=r.points, valid=r.valid, rig_poses=t.rig, rig_poses_end=t.rig_end, rolling=rolling,
+                        shape=r.valid.shape)
+  _rigs[key] = out
+  return out
+
+
+def dense_rig(cameras, frames, rolling, boards=24, seed=202, noise=NOISE_PX, model="standard", share=True):
+  """The rig of the size-edge tests: the FIRST n observations of a frame (camera, then board, then point: the records' order) are a
+  well-posed problem at every n, static and rolling, and past 576 / C of them they come from more than one camera.
+
+    boards   `boards` small grids of 6 x 4 points (0.02 m pitch) with a small tilt and stagger each, in 3 rows 0.35 m apart and
+             columns 0.14 m apart; board b sits in row b % 3 of column b // 3, so the first 63 observations of a camera cover all
+             three rows of the image -- the spread of scan times that tells the start of a rolling-shutter frame from its end.  The
+             points of a board are stored in a fixed shuffled order: the first three or four are not on one line;
+    share    a column of three boards belongs to camera (b // 3) % C alone, so with 24 boards a camera holds 576 / C observations and
+             the first n cross from camera to camera (C = 8: 72 each; C = 3: 192 each); share=False: every camera sees every point;
+    poses    cameras and camera poses of make_rig (the stereo bar); the rig 2 m in front of the boards, rotated by ~0.1 rad.
+
+  Pixels go through multical_amd.synthetic._project (rolling shutter: the scan time of the noisy observed row, as synthetic.make_rig
+  makes its detections consistent) and are kept wherever the point is in front of the camera inside the monotone range of the radial
+  model -- the image border is not a limit here."""
+  key = ("dense", cameras, frames, rolling, boards, seed, noise, str(model), share)
+  if key in _rigs:
+    return _rigs[key]
+  base = make_rig(cameras, 1, model, rolling, frames=frames, seed=seed, noise=0.0)
+  rng = np.random.default_rng(seed)
+  gx, gy = np.mgrid[0:6, 0:4]
+  grid = np.stack([0.02 * gx.ravel(), 0.02 * gy.ravel(), np.zeros(gx.size)], axis=1)[np.random.default_rng(0).permutation(gx.size)]
+  P = len(grid)
+  cols = (boards + 2) // 3
+  board_poses = np.stack([synthetic.to_matrix(np.concatenate([rng.normal(0, 0.05, 3), [0.14 * (b // 3 - (cols - 1) / 2) - 0.05,
+                                                                                    0.35 * (b % 3 - 1) - 0.03, 0.02 * (b % 4)]]))
+                          for b in range(boards)])
+  rig_poses = synthetic.to_matrix(np.concatenate([rng.normal(0, 0.1, (frames, 3)), [0.0, 0.0, 2.0] + rng.normal(0, 0.05, (frames, 3))], axis=1))
+  rig_end = synthetic.to_matrix(rng.normal(0, 5e-3, (frames, 6))) @ rig_poses if rolling else None
+  world = np.einsum('bij,pj->bpi', board_poses[:, :3, :3], grid) + board_poses[:, None, :3, 3]
+  own = np.ones((cameras, boards, P), dtype=bool)
+  if share:
+    own = np.broadcast_to(((np.arange(boards)[None, :] // 3) % cameras == np.arange(cameras)[:, None])[:, :, None], own.shape)
+  points, valid = np.zeros((cameras, frames, boards, P, 2)), np.zeros((cameras, frames, boards, P), dtype=bool)
+  for c, cam in enumerate(base.cameras):
+    def local(poses):
+      T = base.camera_poses[c][None] @ poses
+      return np.einsum('fij,bpj->fbpi', T[:, :3, :3], world) + T[:, None, None, :3, 3]
+    X0 = local(rig_poses)
+    gauss = rng.normal(0.0, noise, X0.shape[:-1] + (2,))
+    Xc = X0
+    ok = np.broadcast_to(own[c][None], X0.shape[:-1]).copy()
+    if rolling:
+      X1 = local(rig_end)
+      h = cam.image_size[1]
+      uv = synthetic._project(cam, X0)
+      for _ in range(6):
+        t = (uv[..., 1] / h)[..., None]
+        uv = synthetic._project(cam, X0 * (1 - t) + X1 * t)
+      t = ((uv + gauss)[..., 1] / h)[..., None]
+      Xc = X0 * (1 - t) + X1 * t
+      for Xq in (X0, X1):
+        ok &= (Xq[..., 2] > 0.1) & (np.hypot(Xq[..., 0], Xq[..., 1]) < 0.62 * Xq[..., 2])
+    uv = synthetic._project(cam, Xc) + gauss
+    ok &= (Xc[..., 2] > 0.1) & (np.hypot(Xc[..., 0], Xc[..., 1]) < 0.62 * Xc[..., 2]) & np.isfinite(uv).all(axis=-1)
+    points[c], valid[c] = np.where(ok[..., None], uv, 0.0), ok
+  out = SimpleNamespace(**vars(base))
+  out.board_poses, out.rig_poses, out.rig_poses_end = board_poses, rig_poses, rig_end
+  out.board_points, out.points, out.valid, out.shape = [grid] * boards, points, valid, valid.shape
+  _rigs[key] = out
+  return out
+
+
+def named_rig(name, **kwargs):
+  return make_rig(*RIGS[name], **kwargs)
+
+
+def keep_first(rig, n, picks=None):
+  """the rig with only the first n observations of every frame (camera, then board, then point order: the records' own); picks:
+  the ordinal numbers (from 0) of the observations to keep instead"""
+  Cn, F, B, P = rig.shape
+  v = np.moveaxis(rig.valid, 1, 0).reshape(F, -1)
+  order = np.cumsum(v, axis=1)
+  keep = v & (order <= n if picks is None else np.isin(order - 1, list(picks)))
+  valid = np.ascontiguousarray(np.moveaxis(keep.reshape(F, Cn, B, P), 0, 1))
+  out = SimpleNamespace(**vars(rig))
+  out.valid = valid
+  out.points = np.where(valid[..., None], rig.points, 0.0)
+  return out
+
+
+def first_frames(rig, F):
+  out = SimpleNamespace(**vars(rig))
+  out.points, out.valid = np.ascontiguousarray(rig.points[:, :F]), np.ascontiguousarray(rig.valid[:, :F])
+  out.rig_poses = rig.rig_poses[:F]
+  out.rig_poses_end = None if rig.rig_poses_end is None else rig.rig_poses_end[:F]
+  out.shape = out.valid.shape
+  return out
+
+
+def run(rig, backend=None, **kwargs):
+  """localise the rig's table through the host build (backend=None) or through the library (backend="device")"""
+  args = (rig.cameras, rig.camera_poses, rig.board_poses, rig.board_points, rig.points, rig.valid)
+  kw = dict(rolling=rig.rolling)
+  kw.update(kwargs)
+  if backend == "device":
+    return localize.localize_rig(*args, **kw)
+  return on_host(localize.localize_rig, *args, **kw)
+
+
+def params(poses):
+  """[n, 6] global rotation vector | translation of [n, 4, 4]"""
+  from scipy.spatial.transform import Rotation
+  poses = np.asarray(poses).reshape(-1, 4, 4)
+  return np.concatenate([Rotation.from_matrix(poses[:, :3, :3]).as_rotvec(), poses[:, :3, 3]], axis=1)
+
+
+def result_params(r):
+  """[F, k] parameters of a result (start, then end)"""
+  p = params(r.poses)
+  return p if r.poses_end is None else np.concatenate([p, params(r.poses_end)], axis=1)
+
+
+def whitened(H, d):
+  """sqrt(d^T H d) per frame"""
+  return np.sqrt(np.maximum(np.einsum('ni,nij,nj->n', d, H, d), 0.0))
+
+
+# ---- the raw call (what the wrapper never sends: NULL arrays, too many cameras) --------------------------------------------------
+def raw_problem(rig, n_cameras=None, **kwargs):
+  """(mcba_rig_pose_problem, outputs, keep-alive) of the rig's table; n_cameras: claim that many cameras (only for calls that are
+  refused before anything is read)"""
+  cams = rig.cameras if n_cameras is None else [rig.cameras[c % len(rig.cameras)] for c in range(n_cameras)]
+  if n_cameras is None:
+    inp = localize.RigPoseInputs(cams, rig.camera_poses, rig.board_poses, rig.board_points, rig.points, rig.valid, rolling=rig.rolling,
+                                 **kwargs)
+    return inp.struct(), inp.outputs(), inp
+  inp = localize.RigPoseInputs(rig.cameras, rig.camera_poses, rig.board_poses, rig.board_points, rig.points, rig.valid,
+                               rolling=rig.rolling, **kwargs)
+  from multical_amd.undistort import CameraSetInputs
+  many = CameraSetInputs(cams)
+  p = inp.struct()
+  p.cams = many.struct()
+  return p, inp.outputs(), [inp, many]
+
+
+def raw_call(fn, p, out, full=False):
+  """rc of fn(problem, poses, ..., status): every optional output NULL unless full"""
+  from multical_amd.undistort import _dp
+  i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+  u8 = out.status.ctypes.data_as(C.POINTER(C.c_uint8))
+  if full:
+    return fn(C.byref(p), _dp(out.poses), _dp(out.poses_end), _dp(out.cov), _dp(out.sse), i32(out.n_obs), i32(out.iters), _dp(out.error), u8)
+  return fn(C.byref(p), _dp(out.poses), None, None, None, None, None, None, u8)
+
+
+def score_candidates(rig, f, candidates):
+  """(scores [n], picked) of the header's scoring step for frame f"""
+  from multical_amd.undistort import _dp
+  p, _, keep = raw_problem(rig)
+  cand = np.ascontiguousarray(np.asarray(candidates, dtype=np.float64).reshape(-1, 4, 4))
+  scores, picked = np.zeros(len(cand)), C.c_int32(-1)
+  if lib().lh_score_candidates(C.byref(p), f, len(cand), _dp(cand), _dp(scores), C.byref(picked)) != 0:
+    raise RuntimeError(lib().lh_last_error().decode())
+  return scores, int(picked.value)
