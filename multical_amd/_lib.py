@@ -6,6 +6,8 @@ is missing, `load()` raises with the build command; if no gfx950 device is prese
 import ctypes as C
 import os
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MCBA_LIB_PATH") or os.path.join(HERE, "_build", "libmcba.so")   # (override: kernel experiments)
 
@@ -250,3 +252,37 @@ def check(rc):
     if "not finite" in msg:
       raise ValueError(msg)
     raise McbaError(msg)
+
+
+# ---- what the wrappers of the handle-less entry points share -----------------------------------------------------------------
+def f64(a):
+  return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+
+
+def u8(a, shape, what):
+  a = np.ascontiguousarray(np.asarray(a).astype(np.uint8))
+  assert a.shape == shape, f"{what} is {a.shape}, not {shape}"
+  return a
+
+
+def _pointer_cast(ctype):
+  pointer = C.POINTER(ctype)
+  return lambda a: None if a is None else a.ctypes.data_as(pointer)
+
+
+# the array's data as double* / int32_t* / uint8_t* / float*; None (an argument left out) stays None
+dp, ip, up, fp = (_pointer_cast(t) for t in (C.c_double, C.c_int32, C.c_uint8, C.c_float))
+
+
+def entry(name):
+  """The library function behind a wrapper: raises with the library's message.  (Every wrapper module calls it through its own
+  `_entry` attribute: the host tests put the g++ build of the same header there.)"""
+  fn = getattr(load(), "mcba_" + name)
+  return lambda *args: check(fn(*args))
+
+
+def call_ms(getter, labels):
+  """mcba_debug_<getter>_ms of this thread's last call of that family: (dict(label -> milliseconds), the family's count)."""
+  ms, n = np.zeros(len(labels)), C.c_int64(0)
+  check(getattr(load(), f"mcba_debug_{getter}_ms")(dp(ms), C.byref(n)))
+  return dict(zip(labels, ms)), int(n.value)

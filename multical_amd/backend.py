@@ -14,24 +14,20 @@ import numpy as np
 
 from . import _lib
 from ._lib import (Problem, Options, Result, RoundReport, LOSSES, OPT_BITS, PARAM_ORDER, MOTION_STATIC, MOTION_ROLLING,
-                   MOTION_HAND_EYE, CAMERA_PINHOLE, CAMERA_FISHEYE, check)
+                   MOTION_HAND_EYE, CAMERA_PINHOLE, CAMERA_FISHEYE, check, f64 as _f64)
 
 
 def _ptr(a, ctype):
   return a.ctypes.data_as(C.POINTER(ctype))
 
 
-def _u8(a):
+def _mask_u8(a):
   a = np.asarray(a)
   if a.dtype == np.bool_ and a.flags.c_contiguous:
     return a.view(np.uint8)          # masks are bool tables of millions of slots: reinterpret, do not copy
   if a.dtype == np.uint8 and a.flags.c_contiguous:
     return a
   return np.ascontiguousarray(a.astype(np.uint8))
-
-
-def _f64(a):
-  return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
 
 def _class_name(obj):
@@ -57,12 +53,12 @@ def lower(calib):
   points = np.asarray(points)
   p.points_f32 = np.ascontiguousarray(points) if points.dtype == np.float32 else None
   p.points = None if p.points_f32 is not None else _f64(points)
-  p.point_valid = _u8(calib.point_table.valid)
-  p.inlier_mask = None if calib.inlier_mask is None else _u8(calib.inlier_mask)
+  p.point_valid = _mask_u8(calib.point_table.valid)
+  p.inlier_mask = None if calib.inlier_mask is None else _mask_u8(calib.inlier_mask)
   p.board_sizes = np.ascontiguousarray(np.array([b.num_points for b in calib.boards], dtype=np.int32))
-  p.camera_valid = _u8(calib.camera_poses.valid)
-  p.board_valid = _u8(calib.board_poses.valid)
-  p.frame_valid = _u8(calib.motion.valid)
+  p.camera_valid = _mask_u8(calib.camera_poses.valid)
+  p.board_valid = _mask_u8(calib.board_poses.valid)
+  p.frame_valid = _mask_u8(calib.motion.valid)
 
   motion = calib.motion
   mname = _class_name(motion)
@@ -94,7 +90,7 @@ def lower(calib):
       raise ValueError(f"fisheye cameras carry 4 distortion coefficients, got {sorted(set(nds))}")
     p.camera_n_dist = np.ascontiguousarray(np.array(nds, dtype=np.int32))
   p.image_heights = _f64([c.image_size[1] for c in cams])
-  p.fix_aspect = _u8([bool(c.fix_aspect) for c in cams])
+  p.fix_aspect = _mask_u8([bool(c.fix_aspect) for c in cams])
 
   p.optimize = _optimize_bits(calib.optimize)
   # all five parameter blocks in reference order (calibration.py:146-153), enabled or not.  (`param_vec` is a cached
@@ -220,7 +216,7 @@ class Handle(object):
     if mask is None:
       check(self.lib.mcba_set_inliers(self.h, None))
     else:
-      m = _u8(mask)
+      m = _mask_u8(mask)
       assert m.shape == tuple(self.shape), f"inlier mask shape {m.shape} != {self.shape}"
       check(self.lib.mcba_set_inliers(self.h, _ptr(m, C.c_uint8)))
 
@@ -325,7 +321,7 @@ class Handle(object):
     F = int(self.shape[1])
     hold_u8 = None
     if hold is not None:
-      hold_u8 = _u8(np.asarray(hold).astype(bool))
+      hold_u8 = _mask_u8(np.asarray(hold).astype(bool))
       assert hold_u8.shape == (self.n_params,), f"hold mask of length {hold_u8.size}, expected {self.n_params}"
     shared = np.empty((n_shared, n_shared))
     fr = np.empty((F, DF, DF)) if frames else None
@@ -359,7 +355,7 @@ class Handle(object):
     x = self._x(x)
     hold_u8 = None
     if hold is not None:
-      hold_u8 = _u8(np.asarray(hold).astype(bool))
+      hold_u8 = _mask_u8(np.asarray(hold).astype(bool))
       assert hold_u8.shape == (self.n_params,), f"hold mask of length {hold_u8.size}, expected {self.n_params}"
     shape = tuple(self.shape)
     pc = np.empty(shape + (3,)) if cov else None

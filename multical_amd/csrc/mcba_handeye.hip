@@ -18,11 +18,12 @@ void hand_eye_launch(const HandEyeArgs& a, hipStream_t st) {
 using namespace mcba;
 using namespace mcba::host;
 
+// plan | uploads | kernel | downloads; problems
+MCBA_TIMING_GETTER(mcba_debug_hand_eye_ms, g_hand_eye_timing, 4)
+
 extern "C" {
 
 namespace {
-thread_local CallTiming g_hand_eye_timing;   // plan | uploads | kernel | downloads; problems
-
 void hand_eye(const mcba_hand_eye_problem& p, double* X, double* Z, int32_t* n_pairs, uint8_t* status, double* err) {
   DeviceCall call(g_hand_eye_timing);   // (before the buffers: see the type)
   handeye::Plan plan;
@@ -34,23 +35,23 @@ void hand_eye(const mcba_hand_eye_problem& p, double* X, double* Z, int32_t* n_p
   call.open();
   const hipStream_t st = call.st;
   const size_t np_ = (size_t)p.n_problems, F = (size_t)p.F, na = (size_t)p.n_a * F, nb = (size_t)p.n_b * F;
-  DevBuf<double> d_ta(na * 16), d_tb, d_out(np_ * 32), d_err;       // d_out: X [np][16] | Z [np][16]
+  DevBuf<double> d_ta(na * 16), d_tb, d_out(np_ * 32);              // d_out: X [np][16] | Z [np][16]
   DevBuf<uint8_t> d_va(na), d_vb, d_status(np_);
   DevBuf<int32_t> d_idx(2 * np_), d_n(np_);                          // d_idx: index_a [np] | index_b [np]
   if (!plan.same_table) {
     d_tb.alloc(nb * 16, false);
     d_vb.alloc(nb, false);
   }
-  if (err) d_err.alloc(np_ * F, false);
+  OutBuf<double> o_err(err, np_ * F);
   call.stamp();
-  HIP_OK(hipMemcpyAsync(d_ta.p, p.table_a, na * 16 * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_va.p, p.valid_a, na, hipMemcpyHostToDevice, st));
+  upload_async(d_ta, p.table_a, na * 16, st);   // (the buffers are sized above: nothing is allocated here)
+  upload_async(d_va, p.valid_a, na, st);
   if (!plan.same_table) {
-    HIP_OK(hipMemcpyAsync(d_tb.p, p.table_b, nb * 16 * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_vb.p, p.valid_b, nb, hipMemcpyHostToDevice, st));
+    upload_async(d_tb, p.table_b, nb * 16, st);
+    upload_async(d_vb, p.valid_b, nb, st);
   }
-  HIP_OK(hipMemcpyAsync(d_idx.p, p.index_a, np_ * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_idx.p + np_, p.index_b, np_ * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  upload_to(d_idx.p, p.index_a, np_, st);
+  upload_to(d_idx.p + np_, p.index_b, np_, st);
   HIP_OK(hipStreamSynchronize(st));
   call.stamp();
   handeye::HandEyeArgs a;
@@ -58,16 +59,16 @@ void hand_eye(const mcba_hand_eye_problem& p, double* X, double* Z, int32_t* n_p
   a.table_a = d_ta.p; a.valid_a = d_va.p;
   a.table_b = plan.same_table ? d_ta.p : d_tb.p; a.valid_b = plan.same_table ? d_va.p : d_vb.p;
   a.index_a = d_idx.p; a.index_b = d_idx.p + np_;
-  a.X = d_out.p; a.Z = d_out.p + np_ * 16; a.n_pairs = d_n.p; a.status = d_status.p; a.err = err ? d_err.p : nullptr;
+  a.X = d_out.p; a.Z = d_out.p + np_ * 16; a.n_pairs = d_n.p; a.status = d_status.p; a.err = o_err.dev();
   handeye::hand_eye_launch(a, st);
   check_launch("k_hand_eye");
   HIP_OK(hipStreamSynchronize(st));
   call.stamp();
-  if (X) HIP_OK(hipMemcpyAsync(X, d_out.p, np_ * 16 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (Z) HIP_OK(hipMemcpyAsync(Z, d_out.p + np_ * 16, np_ * 16 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (n_pairs) HIP_OK(hipMemcpyAsync(n_pairs, d_n.p, np_ * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (status) HIP_OK(hipMemcpyAsync(status, d_status.p, np_, hipMemcpyDeviceToHost, st));
-  if (err) HIP_OK(hipMemcpyAsync(err, d_err.p, np_ * F * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (X) download_async(X, d_out.p, np_ * 16, st);
+  if (Z) download_async(Z, d_out.p + np_ * 16, np_ * 16, st);
+  if (n_pairs) download_async(n_pairs, d_n.p, np_, st);
+  if (status) download_async(status, d_status.p, np_, st);
+  o_err.fetch(st);
   HIP_OK(hipStreamSynchronize(st));
   call.tm.count = (int64_t)np_;
   call.record();
@@ -88,5 +89,3 @@ int32_t mcba_hand_eye(const mcba_hand_eye_problem* p, double* X, double* Z, int3
 }
 
 }  // extern "C"
-
-MCBA_TIMING_GETTER(mcba_debug_hand_eye_ms, g_hand_eye_timing)

@@ -1,5 +1,7 @@
 // mcba_host.h -- the host runtime of libmcba.so, once for every translation unit with a host driver: error convention of the C ABI,
-// resource cache, the buffers that go through it, and the scaffold of a handle-less call (DeviceCall).  g_error, g_fill_stream,
+// resource cache, the buffers that go through it (DevBuf, PinnedBuf, OutBuf: an output the caller may leave out), the transfers
+// of a call counted in elements, and the scaffold of a handle-less call (DeviceCall: stream, buffers through the cache, timing by
+// host clock or by HIP events into the family's four or five slots).  g_error, g_fill_stream,
 // g_park_on_release and the ResourceCache exist ONCE per library: declared here (hidden: not part of the ABI), defined in mcba_api.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -235,66 +237,144 @@ struct DevBuf {
   }
 };
 
-// a buffer of exactly n elements filled from the host on the call's stream (no zero-fill, no synchronisation)
+// The transfers of a call, on its stream, counted in ELEMENTS (no synchronisation).  upload_to / download_async take plain
+// pointers: a run inside a packed buffer (d_out = pose | sse) is an offset pointer.
+template <class T>
+void upload_to(T* dev, const T* h, size_t n, hipStream_t st) {
+  HIP_OK(hipMemcpyAsync(dev, h, n * sizeof(T), hipMemcpyHostToDevice, st));
+}
+template <class T>
+void download_async(T* h, const T* dev, size_t n, hipStream_t st) {
+  HIP_OK(hipMemcpyAsync(h, dev, n * sizeof(T), hipMemcpyDeviceToHost, st));
+}
+// a buffer of at least n elements filled from the host (not zero-filled; one that is large enough already is not touched)
 template <class T>
 void upload_async(DevBuf<T>& d, const T* h, size_t n, hipStream_t st) {
   d.alloc(n, false);
-  HIP_OK(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, st));
+  upload_to(d.p, h, n, st);
+}
+template <class T>
+void upload_vector(DevBuf<T>& d, const std::vector<T>& h, hipStream_t st) {
+  if (h.empty()) return d.alloc(0, false);
+  upload_async(d, h.data(), h.size(), st);
 }
 
-// The four timing slots of a handle-less family and the count that goes with them (mcba_debug_*_ms): what the slots mean is the
-// family's business.  One thread_local instance per family.
+// An output the caller may leave out: allocated only if the host pointer is there, dev() null for the kernel if not, fetch()
+// downloads it if it is (to `to`, where the result goes through a staging array first).  Declared AFTER the call object.
+template <class T>
+struct OutBuf {
+  T* host;
+  size_t n;
+  DevBuf<T> d;
+  OutBuf(T* host_or_null, size_t count) : host(host_or_null), n(count) {
+    if (host) d.alloc(n, false);
+  }
+  T* dev() const { return host ? d.p : nullptr; }
+  void fetch(hipStream_t st, T* to = nullptr) const {
+    if (host) download_async(to ? to : host, d.p, n, st);
+  }
+};
+
+// The timing slots of a handle-less family and the count that goes with them (mcba_debug_*_ms): what the slots mean is the
+// family's business, how many it reports (4, or 5: two event-timed kernels) is stated where its getter is.  One thread_local
+// instance per family (MCBA_TIMING_GETTER).
 struct CallTiming {
-  double ms[4] = {0.0, 0.0, 0.0, 0.0};
+  static constexpr int MAX_SLOTS = 5;
+  double ms[MAX_SLOTS] = {0.0, 0.0, 0.0, 0.0, 0.0};
   int64_t count = 0;
+  int n_slots;
+  constexpr explicit CallTiming(int slots = 4) : n_slots(slots) {}
   void reset(int64_t n = 0) {
     for (double& v : ms) v = 0.0;
     count = n;
   }
-  void report(double* ms_out, int64_t* count_out) const {
+  void report(double* ms_out, int64_t* count_out) const {   // (exactly n_slots doubles: callers of a four-slot family pass double[4])
     REQUIRE(ms_out, "null argument");
-    for (int i = 0; i < 4; ++i) ms_out[i] = ms[i];
+    for (int i = 0; i < n_slots; ++i) ms_out[i] = ms[i];
     if (count_out) *count_out = count;
   }
 };
 
 // One handle-less call on a stream of its own, its buffers going through the resource cache, timed into its family's slots.
-// ORDER: declare it BEFORE every DevBuf / PinnedBuf of the call (or hold them as members of a type derived from it): its destructor
-// then runs AFTER theirs -- they are parked while g_park_on_release still says how the call ended, then the stream goes back and
-// the flag is cleared.
+// ORDER: declare it BEFORE every DevBuf / OutBuf / PinnedBuf of the call (or hold them as members of a type derived from it): its
+// destructor then runs AFTER theirs -- they are parked while g_park_on_release still says how the call ended, then the stream goes
+// back and the flag is cleared.
 //   open()    lazy: a stream from the cache or a new one; a call with nothing to do returns before it, the device untouched
-//   stamp()   the next time stamp (the first is the construction); record(): the last one, and the intervals -> tm.ms[0..]
 //   finish()  the regular end (the stream is synchronised): buffers are parked.  An exception leaves the flag false: they are freed.
+// Two ways to time a call:
+//   by host clock (pose table, intrinsics, hand-eye: plan | uploads | kernel | downloads)
+//     stamp()   the next time stamp (the first is the construction); record(): the last one, and the intervals -> tm.ms[0..]
+//   by HIP events around its n - 1 kernels (undistortion, triangulation: n = 2; localisation: n = 3), n + 2 slots:
+//     open(n)          creates the events; the uploads start here
+//     mark(i)          i == 0: the uploads are complete (synchronises) -> slot 0; records event i
+//     end_kernels()    launch status, synchronises; event i - 1 .. event i -> slot i; the downloads start here
+//     finish(count)    synchronises; downloads -> slot n, the whole call since construction -> slot n + 1, the count; then finish()
 struct DeviceCall {
+  static constexpr int MAX_EVENTS = CallTiming::MAX_SLOTS - 2;
   CallTiming& tm;
   double t[5] = {now_seconds(), 0.0, 0.0, 0.0, 0.0};
   int n_stamps = 1;
   hipStream_t st = nullptr;
+  hipEvent_t ev[MAX_EVENTS] = {};
+  int n_events = 0;
+  double t_up = 0.0, t_down = 0.0;
   explicit DeviceCall(CallTiming& timing) : tm(timing) {}
   DeviceCall(const DeviceCall&) = delete;
-  void open() {
+  void open(int events = 0) {
+    REQUIRE(events == 0 || (events >= 2 && events + 2 <= tm.n_slots), "DeviceCall::open: the family's timing has no slots for these events");
     st = resource_cache().take_stream();
     if (st == nullptr) HIP_OK(hipStreamCreate(&st));
     g_fill_stream = st;
+    for (; n_events < events; ++n_events) HIP_OK(hipEventCreate(&ev[n_events]));
+    t_up = now_seconds();
   }
   void stamp() { t[n_stamps++] = now_seconds(); }
   void record() {
     stamp();
     for (int i = 0; i + 1 < n_stamps; ++i) tm.ms[i] = (t[i + 1] - t[i]) * 1e3;
   }
+  void mark(int i) {
+    if (i == 0) {
+      HIP_OK(hipStreamSynchronize(st));
+      tm.ms[0] = (now_seconds() - t_up) * 1e3;
+    }
+    HIP_OK(hipEventRecord(ev[i], st));
+  }
+  void end_kernels(const char* what) {
+    check_launch(what);
+    HIP_OK(hipStreamSynchronize(st));
+    for (int i = 1; i < n_events; ++i) {
+      float ms = 0.0f;
+      HIP_OK(hipEventElapsedTime(&ms, ev[i - 1], ev[i]));
+      tm.ms[i] = (double)ms;
+    }
+    t_down = now_seconds();
+  }
   void finish() { g_park_on_release = true; }
+  void finish(int64_t count) {
+    HIP_OK(hipStreamSynchronize(st));
+    const double now = now_seconds();
+    tm.ms[n_events] = (now - t_down) * 1e3;
+    tm.ms[n_events + 1] = (now - t[0]) * 1e3;
+    tm.count = count;
+    finish();
+  }
   ~DeviceCall() {
+    for (int i = 0; i < n_events; ++i) (void)hipEventDestroy(ev[i]);
     if (st && !resource_cache().park_stream(st)) (void)hipStreamDestroy(st);
     g_park_on_release = false;
   }
 };
 
-// the mcba_debug_*_ms entry of a family: its four slots and its count
-#define MCBA_TIMING_GETTER(name, timing)                        \
-  extern "C" int32_t name(double* ms, int64_t* count) {         \
-    API_BEGIN                                                   \
-    timing.report(ms, count);                                   \
-    API_END                                                     \
+// a family's timing (thread_local, this unit's own) and its mcba_debug_*_ms entry, which writes `slots` doubles and the count
+#define MCBA_TIMING_GETTER(name, timing, slots)                             \
+  namespace {                                                               \
+  thread_local ::mcba::host::CallTiming timing(slots);                      \
+  }                                                                         \
+  extern "C" int32_t name(double* ms, int64_t* count) {                     \
+    API_BEGIN                                                               \
+    timing.report(ms, count);                                               \
+    API_END                                                                 \
   }
 
 }  // namespace host

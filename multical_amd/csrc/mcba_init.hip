@@ -52,7 +52,7 @@ void align_poses(int32_t n_problems, const int64_t* offsets, const double* A, in
   d_off.alloc((size_t)n_problems + 1, false);
   {
     static_assert(sizeof(long long) == sizeof(int64_t), "offsets are copied as they are");
-    HIP_OK(hipMemcpyAsync(d_off.p, offsets, ((size_t)n_problems + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    upload_to(d_off.p, (const long long*)offsets, (size_t)n_problems + 1, st);
   }
   const size_t tot = (size_t)std::max<int64_t>(total, 1);
   const size_t cntA = ia ? (size_t)nA : tot, cntB = ib ? (size_t)nB : tot;
@@ -60,18 +60,18 @@ void align_poses(int32_t n_problems, const int64_t* offsets, const double* A, in
   const bool same_table = ia != nullptr && A == B && nA == nB;
   if (!same_table) dB.alloc(16 * cntB, false);
   if (total > 0) {
-    HIP_OK(hipMemcpyAsync(dA.p, A, 16 * (ia ? (size_t)nA : (size_t)total) * sizeof(double), hipMemcpyHostToDevice, st));
-    if (!same_table) HIP_OK(hipMemcpyAsync(dB.p, B, 16 * (ib ? (size_t)nB : (size_t)total) * sizeof(double), hipMemcpyHostToDevice, st));
+    upload_to(dA.p, A, 16 * (ia ? (size_t)nA : (size_t)total), st);
+    if (!same_table) upload_to(dB.p, B, 16 * (ib ? (size_t)nB : (size_t)total), st);
     if (ia != nullptr) {
       d_ia.alloc(tot, false);
       d_ib.alloc(tot, false);
-      HIP_OK(hipMemcpyAsync(d_ia.p, ia, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      HIP_OK(hipMemcpyAsync(d_ib.p, ib, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice, st));
+      upload_to(d_ia.p, ia, (size_t)total, st);
+      upload_to(d_ib.p, ib, (size_t)total, st);
     }
   }
   if (mask) {
     d_mask.alloc(tot, false);
-    if (total > 0) HIP_OK(hipMemcpyAsync(d_mask.p, mask, (size_t)total, hipMemcpyHostToDevice, st));
+    if (total > 0) upload_to(d_mask.p, mask, (size_t)total, st);
   }
   d_out.alloc(16 * (size_t)n_problems, false);
   d_valid.alloc((size_t)n_problems, false);
@@ -177,9 +177,9 @@ void align_poses(int32_t n_problems, const int64_t* offsets, const double* A, in
       hipLaunchKernelGGL(k_align_stage_post, dim3(n_problems), dim3(ALIGN_THREADS), 0, st, a, pass);
       check_launch("k_align_stage_post");
     }
-    HIP_OK(hipMemcpyAsync(out, d_out.p, 16 * (size_t)n_problems * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(out_valid, d_valid.p, (size_t)n_problems, hipMemcpyDeviceToHost, st));
-    if (inliers && total > 0) HIP_OK(hipMemcpyAsync(inliers, d_inl.p, (size_t)total, hipMemcpyDeviceToHost, st));
+    download_async(out, d_out.p, 16 * (size_t)n_problems, st);
+    download_async(out_valid, d_valid.p, (size_t)n_problems, st);
+    if (inliers && total > 0) download_async(inliers, d_inl.p, (size_t)total, st);
     HIP_OK(hipStreamSynchronize(st));
     if (timing) {
       std::vector<AlignStage> hs(np_);
@@ -198,9 +198,9 @@ void align_poses(int32_t n_problems, const int64_t* offsets, const double* A, in
                      (const int32_t*)(ib ? d_ib.p : nullptr), (const uint8_t*)(mask ? d_mask.p : nullptr), threshold, (int)invert,
                      (long long)per, sc, d_out.p, d_valid.p, d_inl.p, lds_cap);
   check_launch("k_align_robust");
-  HIP_OK(hipMemcpyAsync(out, d_out.p, 16 * (size_t)n_problems * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(out_valid, d_valid.p, (size_t)n_problems, hipMemcpyDeviceToHost, st));
-  if (inliers && total > 0) HIP_OK(hipMemcpyAsync(inliers, d_inl.p, (size_t)total, hipMemcpyDeviceToHost, st));
+  download_async(out, d_out.p, 16 * (size_t)n_problems, st);
+  download_async(out_valid, d_valid.p, (size_t)n_problems, st);
+  if (inliers && total > 0) download_async(inliers, d_inl.p, (size_t)total, st);
   HIP_OK(hipStreamSynchronize(st));
   if (timing)
     fprintf(stderr, "[align_poses] %d problems, %lld entries: buffers + uploads %.2f ms, kernel + downloads %.2f ms\n", n_problems,

@@ -50,11 +50,12 @@ hipError_t calibrate_camera_launch(const IntrinsicArgs& a, int nd, bool fisheye,
 using namespace mcba;
 using namespace mcba::host;
 
+// plan + gather | uploads | kernels | downloads + scatter; active views
+MCBA_TIMING_GETTER(mcba_debug_calibrate_intrinsics_ms, g_intrinsic_timing, 4)
+
 extern "C" {
 
 namespace {
-thread_local CallTiming g_intrinsic_timing;   // plan + gather | uploads | kernels | downloads + scatter; active views
-
 void calibrate_intrinsics(const mcba_intrinsic_problem& p, double* cameras, double* poses, double* sse, int32_t* n_used,
                           uint8_t* view_status, uint8_t* camera_status) {
   DeviceCall call(g_intrinsic_timing);   // (before the buffers: see the type)
@@ -83,21 +84,21 @@ void calibrate_intrinsics(const mcba_intrinsic_problem& p, double* cameras, doub
   // d_int: n_used [na] | iterations of the start poses [na] | usable views [na] | LM passes [C]
   DevBuf<int32_t> d_desc(2 * na), d_first(nc + 1), d_nd(nc), d_int(3 * na + nc), d_group(h_group.size());
   call.stamp();
-  HIP_OK(hipMemcpyAsync(d_px.p, rows.px, rows.px_bytes, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_ok.p, rows.ok, rows.ok_bytes, hipMemcpyHostToDevice, st));
-  if (plan.warm) HIP_OK(hipMemcpyAsync(d_pose.p, rows.in, rows.in_bytes, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_board.p, p.board_points, (size_t)p.B * P * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_planes.p, plan.planes.data(), plan.planes.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_mask.p, plan.mask.data(), plan.mask.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_size.p, plan.image_size.data(), 2 * nc * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_blk.p, h_blk.data(), h_blk.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_fa.p, plan.cam_fa.data(), nc, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_fish.p, plan.cam_fish.data(), nc, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_cstatus.p, plan.cam_status.data(), nc, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_desc.p, plan.desc.data(), 2 * na * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_first.p, plan.cam_first.data(), (nc + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_nd.p, plan.cam_nd.data(), nc * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_group.p, h_group.data(), h_group.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  upload_async(d_px, rows.px, na * P * 2, st);   // (the buffers are sized above: nothing is allocated here)
+  upload_async(d_ok, rows.ok, na * P, st);
+  if (plan.warm) upload_async(d_pose, rows.in, na * 16, st);
+  upload_async(d_board, p.board_points, (size_t)p.B * P * 3, st);
+  upload_async(d_planes, plan.planes.data(), plan.planes.size(), st);
+  upload_async(d_mask, plan.mask.data(), plan.mask.size(), st);
+  upload_async(d_size, plan.image_size.data(), 2 * nc, st);
+  upload_async(d_blk, h_blk.data(), h_blk.size(), st);
+  upload_async(d_fa, plan.cam_fa.data(), nc, st);
+  upload_async(d_fish, plan.cam_fish.data(), nc, st);
+  upload_async(d_cstatus, plan.cam_status.data(), nc, st);
+  upload_async(d_desc, plan.desc.data(), 2 * na, st);
+  upload_async(d_first, plan.cam_first.data(), nc + 1, st);
+  upload_async(d_nd, plan.cam_nd.data(), nc, st);
+  upload_async(d_group, h_group.data(), h_group.size(), st);
   HIP_OK(hipMemsetAsync(d_vstatus.p, 0, na, st));                       // (warm start: every view is usable)
   HIP_OK(hipMemsetAsync(d_int.p, 0, (3 * na + nc) * sizeof(int32_t), st));
   HIP_OK(hipStreamSynchronize(st));
@@ -130,12 +131,12 @@ void calibrate_intrinsics(const mcba_intrinsic_problem& p, double* cameras, doub
   std::vector<double> h_pose(na * 16), h_sse(na);
   std::vector<int32_t> h_int(3 * na + nc);
   std::vector<uint8_t> h_vstatus(na), h_cstatus(nc);
-  HIP_OK(hipMemcpyAsync(h_blk.data(), d_blk.p, h_blk.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_pose.data(), d_pose.p, na * 16 * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_sse.data(), d_sse.p, na * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_int.data(), d_int.p, h_int.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_vstatus.data(), d_vstatus.p, na, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_cstatus.data(), d_cstatus.p, nc, hipMemcpyDeviceToHost, st));
+  download_async(h_blk.data(), d_blk.p, h_blk.size(), st);
+  download_async(h_pose.data(), d_pose.p, na * 16, st);
+  download_async(h_sse.data(), d_sse.p, na, st);
+  download_async(h_int.data(), d_int.p, h_int.size(), st);
+  download_async(h_vstatus.data(), d_vstatus.p, na, st);
+  download_async(h_cstatus.data(), d_cstatus.p, nc, st);
   HIP_OK(hipStreamSynchronize(st));
   for (int c = 0; c < p.C; ++c) {
     if (plan.cam_first[c + 1] == plan.cam_first[c]) continue;   // (not solved: fill_unsolved has said so)
@@ -174,5 +175,3 @@ int32_t mcba_calibrate_intrinsics(const mcba_intrinsic_problem* p, double* camer
 }
 
 }  // extern "C"
-
-MCBA_TIMING_GETTER(mcba_debug_calibrate_intrinsics_ms, g_intrinsic_timing)

@@ -29,71 +29,16 @@ hipError_t rig_pose_launch(const RigPoseArgs& a, bool rolling, hipStream_t st) {
 using namespace mcba;
 using namespace mcba::host;
 
-namespace {
-template <class T>
-void download_async(T* host, const DevBuf<T>& d, size_t n, hipStream_t st) {
-  HIP_OK(hipMemcpyAsync(host, d.p, n * sizeof(T), hipMemcpyDeviceToHost, st));
-}
-template <class T>
-void upload_vector(DevBuf<T>& d, const std::vector<T>& h, hipStream_t st) {
-  if (h.empty()) return d.alloc(0, false);
-  upload_async(d, h.data(), h.size(), st);
-}
-}  // namespace
+// uploads | start kernel | refinement kernel (HIP events) | downloads | whole call; frames launched
+MCBA_TIMING_GETTER(mcba_debug_rig_poses_ms, g_rig_pose_timing, 5)
 
 extern "C" {
 
 namespace {
-thread_local CallTiming g_rig_pose_timing;   // uploads | start kernel | refinement kernel (HIP events) | downloads; frames launched
-thread_local double g_rig_pose_call_ms = 0.0;
-
-// the scaffold plus the three events around the two kernels (members: they go before the DeviceCall they derive from does)
-struct RigPoseCall : DeviceCall {
-  double t_up = 0.0;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-
-  RigPoseCall() : DeviceCall(g_rig_pose_timing) {
-    tm.reset();
-    g_rig_pose_call_ms = 0.0;
-  }
-  void open() {
-    DeviceCall::open();
-    for (hipEvent_t& e : ev) HIP_OK(hipEventCreate(&e));
-    t_up = now_seconds();
-  }
-  ~RigPoseCall() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  void mark(int i) {
-    if (i == 0) {      // uploads are complete; the kernels run between the events
-      HIP_OK(hipStreamSynchronize(st));
-      tm.ms[0] = (now_seconds() - t_up) * 1e3;
-    }
-    HIP_OK(hipEventRecord(ev[i], st));
-  }
-  double end_kernels() {
-    HIP_OK(hipStreamSynchronize(st));
-    float ms = 0.0f;
-    HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    tm.ms[1] = (double)ms;
-    HIP_OK(hipEventElapsedTime(&ms, ev[1], ev[2]));
-    tm.ms[2] = (double)ms;
-    return now_seconds();
-  }
-  void finish(double t_down, int64_t frames) {
-    HIP_OK(hipStreamSynchronize(st));
-    const double t = now_seconds();
-    tm.ms[3] = (t - t_down) * 1e3;
-    g_rig_pose_call_ms = (t - this->t[0]) * 1e3;
-    tm.count = frames;
-    DeviceCall::finish();
-  }
-};
-
 void run_rig_poses(const mcba_rig_pose_problem* p, double* poses, double* poses_end, double* cov, double* sse, int32_t* n_obs,
                    int32_t* iters, double* err, uint8_t* status) {
-  RigPoseCall call;   // (before the buffers: see host::DeviceCall)
+  DeviceCall call(g_rig_pose_timing);   // (before the buffers: see the type)
+  call.tm.reset();
   localize::Plan plan;
   std::string msg;
   bool empty = true;
@@ -106,11 +51,11 @@ void run_rig_poses(const mcba_rig_pose_problem* p, double* poses, double* poses_
   const size_t F = (size_t)plan.F, N = plan.n_records(), nv = plan.n_views(), P = (size_t)plan.P, KC = (size_t)localize::n_cov(plan.K);
   if (n_obs)
     for (size_t f = 0; f < F; ++f) n_obs[f] = plan.first[f + 1] - plan.first[f];
-  DevBuf<double> d_recs, d_uv, d_W, d_init, d_init_end, d_cam_inv, d_board_inv, d_poses, d_poses_end, d_cov, d_sse, d_err;
+  DevBuf<double> d_recs, d_uv, d_W, d_init, d_init_end, d_cam_inv, d_board_inv, d_poses;
   DevBuf<double> d_vpx, d_board, d_vcam, d_planes, d_vpose, d_vsse;
-  DevBuf<int32_t> d_first, d_ocam, d_owpt, d_iters, d_vfirst, d_vdesc, d_vnd, d_vn, d_vit;
+  DevBuf<int32_t> d_first, d_ocam, d_owpt, d_vfirst, d_vdesc, d_vnd, d_vn, d_vit;
   DevBuf<uint8_t> d_status, d_vok, d_vfish, d_vstatus;
-  call.open();
+  call.open(3);
   const hipStream_t st = call.st;
   upload_vector(d_recs, plan.recs, st);
   upload_vector(d_uv, plan.uv, st);
@@ -148,11 +93,8 @@ void run_rig_poses(const mcba_rig_pose_problem* p, double* poses, double* poses_
   }
   d_poses.alloc(F * 16, false);
   d_status.alloc(F, false);
-  if (poses_end) d_poses_end.alloc(F * 16, false);
-  if (cov) d_cov.alloc(F * KC, false);
-  if (sse) d_sse.alloc(F, false);
-  if (iters) d_iters.alloc(F, false);
-  if (err) d_err.alloc(N, false);
+  OutBuf<double> o_poses_end(poses_end, F * 16), o_cov(cov, F * KC), o_sse(sse, F), o_err(err, N);   // (err: by record, see below)
+  OutBuf<int32_t> o_iters(iters, F);
   call.mark(0);
   if (!p->init && nv > 0) {
     pnp::ViewPoseArgs v;
@@ -173,23 +115,22 @@ void run_rig_poses(const mcba_rig_pose_problem* p, double* poses, double* poses_
   a.view_first = d_vfirst.p; a.view_desc = d_vdesc.p; a.view_pose = d_vpose.p; a.view_n = d_vn.p; a.view_status = d_vstatus.p;
   a.cam_inv = d_cam_inv.p; a.board_inv = d_board_inv.p;
   a.poses = d_poses.p; a.status = d_status.p;
-  a.poses_end = poses_end ? d_poses_end.p : nullptr;
-  a.cov = cov ? d_cov.p : nullptr; a.sse = sse ? d_sse.p : nullptr; a.iters = iters ? d_iters.p : nullptr; a.err = err ? d_err.p : nullptr;
+  a.poses_end = o_poses_end.dev(); a.cov = o_cov.dev(); a.sse = o_sse.dev(); a.iters = o_iters.dev(); a.err = o_err.dev();
   const hipError_t e = localize::rig_pose_launch(a, plan.rolling, st);
   if (e != hipSuccess) throw Error(std::string("kernel launch failed (k_rig_pose): ") + hipGetErrorString(e));
   call.mark(2);
-  const double t_down = call.end_kernels();
+  call.end_kernels("k_rig_pose");
   std::vector<double> err_rec(err ? N : 0);
-  download_async(poses, d_poses, F * 16, st);
-  download_async(status, d_status, F, st);
-  if (poses_end) download_async(poses_end, d_poses_end, F * 16, st);
-  if (cov) download_async(cov, d_cov, F * KC, st);
-  if (sse) download_async(sse, d_sse, F, st);
-  if (iters) download_async(iters, d_iters, F, st);
-  if (err) download_async(err_rec.data(), d_err, N, st);
+  download_async(poses, d_poses.p, F * 16, st);
+  download_async(status, d_status.p, F, st);
+  o_poses_end.fetch(st);
+  o_cov.fetch(st);
+  o_sse.fetch(st);
+  o_iters.fetch(st);
+  o_err.fetch(st, err_rec.data());
   HIP_OK(hipStreamSynchronize(st));
   if (err) localize::scatter_errors(plan, err_rec.data(), err);
-  call.finish(t_down, (int64_t)F);
+  call.finish((int64_t)F);
 }
 }  // namespace
 
@@ -197,13 +138,6 @@ int32_t mcba_rig_poses(const mcba_rig_pose_problem* p, double* poses, double* po
                        int32_t* iters, double* err, uint8_t* status) {
   API_BEGIN
   run_rig_poses(p, poses, poses_end, cov, sse, n_obs, iters, err, status);
-  API_END
-}
-
-int32_t mcba_debug_rig_poses_ms(double* ms, int64_t* n_frames) {
-  API_BEGIN
-  g_rig_pose_timing.report(ms, n_frames);
-  ms[4] = g_rig_pose_call_ms;
   API_END
 }
 

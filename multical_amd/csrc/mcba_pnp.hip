@@ -24,11 +24,12 @@ void view_pose_launch(const ViewPoseArgs& a, hipStream_t st) {
 using namespace mcba;
 using namespace mcba::host;
 
+// plan + gather | uploads | kernel | downloads + scatter; active views
+MCBA_TIMING_GETTER(mcba_debug_view_poses_ms, g_view_pose_timing, 4)
+
 extern "C" {
 
 namespace {
-thread_local CallTiming g_view_pose_timing;   // plan + gather | uploads | kernel | downloads + scatter; active views
-
 void view_poses(const mcba_view_pose_problem& p, double* poses, double* sse, int32_t* n_used, uint8_t* status) {
   DeviceCall call(g_view_pose_timing);   // (before the buffers: see the type)
   pnp::ViewPlan plan;
@@ -50,15 +51,15 @@ void view_poses(const mcba_view_pose_problem& p, double* poses, double* sse, int
   DevBuf<int32_t> d_desc(2 * na), d_nd((size_t)p.C), d_int(na * 2);
   if (p.init_poses) d_in.alloc(na * 16, false);
   call.stamp();
-  HIP_OK(hipMemcpyAsync(d_px.p, rows.px, rows.px_bytes, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_ok.p, rows.ok, rows.ok_bytes, hipMemcpyHostToDevice, st));
-  if (p.init_poses) HIP_OK(hipMemcpyAsync(d_in.p, rows.in, rows.in_bytes, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_board.p, p.board_points, (size_t)p.B * P * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_cam.p, plan.cam.data(), plan.cam.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_planes.p, plan.planes.data(), plan.planes.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_desc.p, plan.desc.data(), 2 * na * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_nd.p, plan.cam_nd.data(), (size_t)p.C * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(d_fish.p, plan.cam_fish.data(), (size_t)p.C, hipMemcpyHostToDevice, st));
+  upload_async(d_px, rows.px, na * P * 2, st);   // (the buffers are sized above: nothing is allocated here)
+  upload_async(d_ok, rows.ok, na * P, st);
+  if (p.init_poses) upload_async(d_in, rows.in, na * 16, st);
+  upload_async(d_board, p.board_points, (size_t)p.B * P * 3, st);
+  upload_async(d_cam, plan.cam.data(), plan.cam.size(), st);
+  upload_async(d_planes, plan.planes.data(), plan.planes.size(), st);
+  upload_async(d_desc, plan.desc.data(), 2 * na, st);
+  upload_async(d_nd, plan.cam_nd.data(), (size_t)p.C, st);
+  upload_async(d_fish, plan.cam_fish.data(), (size_t)p.C, st);
   HIP_OK(hipStreamSynchronize(st));
   call.stamp();
   pnp::ViewPoseArgs a;
@@ -73,9 +74,9 @@ void view_poses(const mcba_view_pose_problem& p, double* poses, double* sse, int
   std::vector<double> h_out(na * 17);
   std::vector<int32_t> h_int(na * 2);
   std::vector<uint8_t> h_status(na);
-  HIP_OK(hipMemcpyAsync(h_out.data(), d_out.p, na * 17 * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_int.data(), d_int.p, na * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipMemcpyAsync(h_status.data(), d_status.p, na, hipMemcpyDeviceToHost, st));
+  download_async(h_out.data(), d_out.p, na * 17, st);
+  download_async(h_int.data(), d_int.p, na * 2, st);
+  download_async(h_status.data(), d_status.p, na, st);
   HIP_OK(hipStreamSynchronize(st));
   for (size_t k = 0; k < na; ++k) {
     const size_t v = (size_t)plan.active[k];
@@ -103,5 +104,3 @@ int32_t mcba_view_poses(const mcba_view_pose_problem* p, double* poses, double* 
 }
 
 }  // extern "C"
-
-MCBA_TIMING_GETTER(mcba_debug_view_poses_ms, g_view_pose_timing)

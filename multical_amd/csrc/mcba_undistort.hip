@@ -60,59 +60,25 @@ bool remap_launch(const RemapArgs& a, int channels, int dtype, bool fused, hipSt
 using namespace mcba;
 using namespace mcba::host;
 
+// uploads | event-timed kernel | downloads | whole call; pixels written
+MCBA_TIMING_GETTER(mcba_debug_undistort_ms, g_undistort_timing, 4)
+
 extern "C" {
 
 namespace {
-thread_local CallTiming g_undistort_timing;   // uploads | event-timed kernel | downloads | whole call; pixels written
-
-// what every undistortion call shares beyond the scaffold: the events around the kernel and the camera tables on the device
-// (members: they go before the DeviceCall they derive from does)
+// what every undistortion call shares beyond the scaffold: the camera tables on the device (members: they go before the DeviceCall
+// they derive from does)
 struct UndistortCall : DeviceCall {
-  double t_up = 0.0;
-  hipEvent_t ev[2] = {nullptr, nullptr};
   DevBuf<double> d_cam, d_iR;
   DevBuf<int32_t> d_nd;
   DevBuf<uint8_t> d_fish;
 
   UndistortCall() : DeviceCall(g_undistort_timing) { tm.reset(); }
-  void open() {
-    DeviceCall::open();
-    HIP_OK(hipEventCreate(&ev[0]));
-    HIP_OK(hipEventCreate(&ev[1]));
-    t_up = now_seconds();
-  }
-  ~UndistortCall() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
   undistort::CameraTable cameras(const undistort::CameraPlan& plan) {
-    upload_async(d_cam, plan.cam.data(), plan.cam.size(), st);
-    upload_async(d_nd, plan.cam_nd.data(), plan.cam_nd.size(), st);
-    upload_async(d_fish, plan.cam_fish.data(), plan.cam_fish.size(), st);
+    upload_vector(d_cam, plan.cam, st);
+    upload_vector(d_nd, plan.cam_nd, st);
+    upload_vector(d_fish, plan.cam_fish, st);
     return undistort::CameraTable{d_cam.p, d_nd.p, d_fish.p};
-  }
-  // uploads are complete; the kernel runs between the two events
-  void begin_kernel() {
-    HIP_OK(hipStreamSynchronize(st));
-    tm.ms[0] = (now_seconds() - t_up) * 1e3;
-    HIP_OK(hipEventRecord(ev[0], st));
-  }
-  double end_kernel(const char* what) {
-    check_launch(what);
-    HIP_OK(hipEventRecord(ev[1], st));
-    HIP_OK(hipStreamSynchronize(st));
-    float ms = 0.0f;
-    HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    tm.ms[1] = (double)ms;
-    return now_seconds();
-  }
-  void finish(double t_down, int64_t pixels) {
-    HIP_OK(hipStreamSynchronize(st));
-    const double t = now_seconds();
-    tm.ms[2] = (t - t_down) * 1e3;
-    tm.ms[3] = (t - this->t[0]) * 1e3;
-    tm.count = pixels;
-    DeviceCall::finish();
   }
 };
 
@@ -129,8 +95,7 @@ void point_ops(const char* who, bool undist, const mcba_camera_set* cams, int64_
   const size_t N = (size_t)n, C_ = (size_t)cams->C, w = undist ? 2 : 3;
   DevBuf<double> d_in, d_out, d_R, d_P;
   DevBuf<int32_t> d_of;
-  DevBuf<uint8_t> d_status;
-  call.open();
+  call.open(2);
   undistort::PointOpsArgs a{};
   a.undistort = undist ? 1 : 0;
   a.n = n;
@@ -140,15 +105,16 @@ void point_ops(const char* who, bool undist, const mcba_camera_set* cams, int64_
   if (R) upload_async(d_R, R, C_ * 9, call.st);
   if (P) upload_async(d_P, P, C_ * 9, call.st);
   d_out.alloc(N * 2, false);
-  if (undist) d_status.alloc(N, false);
+  OutBuf<uint8_t> o_status(undist ? status : nullptr, N);
   a.camera_of = camera_of ? d_of.p : nullptr;
-  a.in = d_in.p; a.R = R ? d_R.p : nullptr; a.P = P ? d_P.p : nullptr; a.out = d_out.p; a.status = undist ? d_status.p : nullptr;
-  call.begin_kernel();
+  a.in = d_in.p; a.R = R ? d_R.p : nullptr; a.P = P ? d_P.p : nullptr; a.out = d_out.p; a.status = o_status.dev();
+  call.mark(0);
   undistort::point_ops_launch(a, call.st);
-  const double t_down = call.end_kernel("k_point_ops");
-  HIP_OK(hipMemcpyAsync(out, d_out.p, N * 2 * sizeof(double), hipMemcpyDeviceToHost, call.st));
-  if (undist) HIP_OK(hipMemcpyAsync(status, d_status.p, N, hipMemcpyDeviceToHost, call.st));
-  call.finish(t_down, n);
+  call.mark(1);
+  call.end_kernels("k_point_ops");
+  download_async(out, d_out.p, N * 2, call.st);
+  o_status.fetch(call.st);
+  call.finish(n);
 }
 
 void undistort_maps(const mcba_camera_set* cams, const double* R, const double* P, int32_t width, int32_t height, float* maps) {
@@ -163,18 +129,19 @@ void undistort_maps(const mcba_camera_set* cams, const double* R, const double* 
   REQUIRE(maps, "mcba_undistort_maps: null argument");
   const size_t total = (size_t)cams->C * height * width;
   DevBuf<float> d_maps;
-  call.open();
+  call.open(2);
   undistort::MapArgs a{};
   a.t = call.cameras(plan);
-  upload_async(call.d_iR, iR.data(), iR.size(), call.st);
+  upload_vector(call.d_iR, iR, call.st);
   a.iR = call.d_iR.p; a.C = cams->C; a.H = height; a.W = width;
   d_maps.alloc(total * 2, false);
   a.maps = d_maps.p;
-  call.begin_kernel();
+  call.mark(0);
   undistort::undistort_map_launch(a, call.st);
-  const double t_down = call.end_kernel("k_undistort_map");
-  HIP_OK(hipMemcpyAsync(maps, d_maps.p, total * 2 * sizeof(float), hipMemcpyDeviceToHost, call.st));
-  call.finish(t_down, (int64_t)total);
+  call.mark(1);
+  call.end_kernels("k_undistort_map");
+  download_async(maps, d_maps.p, total * 2, call.st);
+  call.finish((int64_t)total);
 }
 
 // maps != nullptr: remap through the given maps; else the fused form through the cameras
@@ -203,16 +170,16 @@ void remap_images(const char* who, const mcba_camera_set* cams, const double* R,
   DevBuf<uint8_t> d_src, d_dst;
   DevBuf<float> d_maps;
   DevBuf<int32_t> d_index, d_by_camera;
-  call.open();
+  call.open(2);
   undistort::RemapArgs a{};
   std::vector<int32_t> by_camera;        // camera_start [M + 1] | camera_images [N]
   if (fused) {
     a.t = call.cameras(plan);
-    upload_async(call.d_iR, iR.data(), iR.size(), call.st);
+    upload_vector(call.d_iR, iR, call.st);
     a.iR = call.d_iR.p;
     a.C = M;
     undistort::images_by_camera(index, N, M, by_camera);
-    upload_async(d_by_camera, by_camera.data(), by_camera.size(), call.st);
+    upload_vector(d_by_camera, by_camera, call.st);
     a.camera_start = d_by_camera.p;
     a.camera_images = d_by_camera.p + M + 1;
   } else {
@@ -226,11 +193,12 @@ void remap_images(const char* who, const mcba_camera_set* cams, const double* R,
   a.N = N; a.Hs = Hs; a.Ws = Ws; a.Hd = Hd; a.Wd = Wd;
   a.border = (float)border;
   a.flat = (Wd % 4 != 0) ? 1 : 0;
-  call.begin_kernel();
+  call.mark(0);
   REQUIRE(undistort::remap_launch(a, channels, dtype, fused, call.st), std::string(who) + ": no kernel for this image format");
-  const double t_down = call.end_kernel("k_remap_cubic");
-  HIP_OK(hipMemcpyAsync(dst, d_dst.p, dst_bytes, hipMemcpyDeviceToHost, call.st));
-  call.finish(t_down, (int64_t)N * Hd * Wd);
+  call.mark(1);
+  call.end_kernels("k_remap_cubic");
+  download_async((uint8_t*)dst, d_dst.p, dst_bytes, call.st);
+  call.finish((int64_t)N * Hd * Wd);
 }
 }  // namespace
 
@@ -271,5 +239,3 @@ int32_t mcba_undistort_images(const mcba_camera_set* cams, const double* R, cons
 }
 
 }  // extern "C"
-
-MCBA_TIMING_GETTER(mcba_debug_undistort_ms, g_undistort_timing)

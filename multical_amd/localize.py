@@ -12,34 +12,13 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import dp as _dp, entry as _entry, f64 as _f64, ip as _ip, u8 as _u8, up as _up   # noqa: F401 (_entry: see _lib.entry)
 from .structs import struct
-from .undistort import CameraSetInputs, _dp, _f64
+from .undistort import CameraSetInputs
 
 OK, TOO_FEW, DEGENERATE, NOT_CONVERGED, BEHIND = (_lib.RIG_OK, _lib.RIG_TOO_FEW, _lib.RIG_DEGENERATE, _lib.RIG_NOT_CONVERGED,
                                                   _lib.RIG_BEHIND)
 MAX_CAMERAS = _lib.RIG_MAX_CAMERAS
-
-
-def _entry(name):
-  """The library function behind a wrapper: raises with the library's message.  (The host tests put the g++ build of the same
-  header here.)"""
-  fn = getattr(_lib.load(), "mcba_" + name)
-  return lambda *args: check(fn(*args))
-
-
-def _u8(a, shape, what):
-  a = np.ascontiguousarray(np.asarray(a).astype(np.uint8))
-  assert a.shape == shape, f"{what} is {a.shape}, not {shape}"
-  return a
-
-
-def _up(a):
-  return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
-
-
-def _i32p(a):
-  return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 def covariance_matrices(tri, K):
@@ -116,7 +95,7 @@ def localize_rig(cameras, camera_poses, board_poses, board_points, points, valid
                       init_end=init_end, rolling=rolling, sigma=sigma, max_iterations=max_iterations)
   out = inp.outputs()
   p = inp.struct()
-  _entry("rig_poses")(C.byref(p), _dp(out.poses), _dp(out.poses_end), _dp(out.cov), _dp(out.sse), _i32p(out.n_obs), _i32p(out.iters),
+  _entry("rig_poses")(C.byref(p), _dp(out.poses), _dp(out.poses_end), _dp(out.cov), _dp(out.sse), _ip(out.n_obs), _ip(out.iters),
                       _dp(out.error), _up(out.status))
   return struct(poses=out.poses, poses_end=out.poses_end if inp.rolling else None, cov=covariance_matrices(out.cov, inp.K), sse=out.sse,
                 n_obs=out.n_obs, iters=out.iters, error=out.error, status=out.status)
@@ -125,6 +104,4 @@ def localize_rig(cameras, camera_poses, board_poses, board_points, points, valid
 def last_call_ms():
   """mcba_debug_rig_poses_ms of this thread's last call: (dict(upload, start_kernel, kernel, download, call) in milliseconds, frames
   launched)."""
-  ms, n = np.zeros(5), C.c_int64(0)
-  check(_lib.load().mcba_debug_rig_poses_ms(_dp(ms), C.byref(n)))
-  return dict(upload=ms[0], start_kernel=ms[1], kernel=ms[2], download=ms[3], call=ms[4]), int(n.value)
+  return _lib.call_ms("rig_poses", ("upload", "start_kernel", "kernel", "download", "call"))

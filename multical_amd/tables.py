@@ -20,12 +20,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import check, dp, f64 as _f64, ip, up
 from .structs import Table, struct
-
-
-def _f64(a):
-  return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
 
 def align_transforms_robust_ragged(A, B, sizes, mask=None, threshold=1.5, invert=False):
@@ -46,13 +42,10 @@ def align_transforms_robust_ragged(A, B, sizes, mask=None, threshold=1.5, invert
   out = np.empty((P, 4, 4))
   valid = np.empty(P, dtype=np.uint8)
   inl = np.empty(max(total, 1), dtype=np.uint8)
-  dp = C.POINTER(C.c_double)
-  up = C.POINTER(C.c_uint8)
   import os, time
   t0 = time.perf_counter()
-  check(lib.mcba_align_poses_robust(P, offsets.ctypes.data_as(C.POINTER(C.c_int64)), A.ctypes.data_as(dp), B.ctypes.data_as(dp),
-                                    None if mask is None else mask.ctypes.data_as(up), float(threshold), 1 if invert else 0,
-                                    out.ctypes.data_as(dp), valid.ctypes.data_as(up), inl.ctypes.data_as(up)))
+  check(lib.mcba_align_poses_robust(P, offsets.ctypes.data_as(C.POINTER(C.c_int64)), dp(A), dp(B), up(mask), float(threshold),
+                                    1 if invert else 0, dp(out), up(valid), up(inl)))
   if os.environ.get("MCBA_TIMING"):
     print(f"[mcba_align_poses_robust] {P} problems, {total} entries, largest {int(sizes.max())}: {(time.perf_counter() - t0) * 1e3:.2f} ms",
           flush=True)
@@ -78,12 +71,9 @@ def align_transforms_robust_indexed(table, index_a, index_b, sizes, mask=None, t
   out = np.empty((P, 4, 4))
   valid = np.empty(P, dtype=np.uint8)
   inl = np.empty(max(total, 1), dtype=np.uint8)
-  dp, up, ip = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
-  tp = table.ctypes.data_as(dp)
-  check(lib.mcba_align_poses_indexed(P, offsets.ctypes.data_as(C.POINTER(C.c_int64)), tp, table.shape[0], ia.ctypes.data_as(ip), tp,
-                                     table.shape[0], ib.ctypes.data_as(ip), None if mask is None else mask.ctypes.data_as(up),
-                                     float(threshold), 1 if invert else 0, out.ctypes.data_as(dp), valid.ctypes.data_as(up),
-                                     inl.ctypes.data_as(up)))
+  tp = dp(table)
+  check(lib.mcba_align_poses_indexed(P, offsets.ctypes.data_as(C.POINTER(C.c_int64)), tp, table.shape[0], ip(ia), tp,
+                                     table.shape[0], ip(ib), up(mask), float(threshold), 1 if invert else 0, dp(out), up(valid), up(inl)))
   return out, valid.astype(bool), inl[:total].astype(bool)
 
 
@@ -273,13 +263,12 @@ class HandEyeInputs(object):
     self.invert = bool(invert)
 
   def struct(self):
-    dp, up, ip = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
     s = _lib.HandEyeProblem()
     s.F, s.n_a, s.n_b = self.F, self.table_a.shape[0], self.table_b.shape[0]
-    s.table_a, s.valid_a = self.table_a.ctypes.data_as(dp), self.valid_a.ctypes.data_as(up)
-    s.table_b, s.valid_b = self.table_b.ctypes.data_as(dp), self.valid_b.ctypes.data_as(up)
+    s.table_a, s.valid_a = dp(self.table_a), up(self.valid_a)
+    s.table_b, s.valid_b = dp(self.table_b), up(self.valid_b)
     s.n_problems = self.n
-    s.index_a, s.index_b = self.index_a.ctypes.data_as(ip), self.index_b.ctypes.data_as(ip)
+    s.index_a, s.index_b = ip(self.index_a), ip(self.index_b)
     s.invert_inputs = 1 if self.invert else 0
     return s
 
@@ -295,9 +284,7 @@ def hand_eye_batch(table_a, valid_a, table_b, valid_b, index_a, index_b, invert=
   inp = HandEyeInputs(table_a, valid_a, table_b, valid_b, index_a, index_b, invert)
   X, Z, n_pairs, status, err = inp.outputs()
   s = inp.struct()
-  dp = C.POINTER(C.c_double)
-  check(_lib.load().mcba_hand_eye(C.byref(s), X.ctypes.data_as(dp), Z.ctypes.data_as(dp), n_pairs.ctypes.data_as(C.POINTER(C.c_int32)),
-                                  status.ctypes.data_as(C.POINTER(C.c_uint8)), err.ctypes.data_as(dp)))
+  check(_lib.load().mcba_hand_eye(C.byref(s), dp(X), dp(Z), ip(n_pairs), up(status), dp(err)))
   return X, Z, n_pairs, status, err
 
 
@@ -367,19 +354,18 @@ class ViewPoseInputs(object):
     self.lm_iterations = np.zeros(self.shape, dtype=np.int32)
 
   def struct(self):
-    dp, up, ip = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
     s = _lib.ViewPoseProblem()
     s.C, s.F, s.B = self.shape
     s.P = self.valid.shape[3]
-    s.points, s.valid = self.points.ctypes.data_as(dp), self.valid.ctypes.data_as(up)
-    s.board_points, s.board_sizes = self.board_points.ctypes.data_as(dp), self.board_sizes.ctypes.data_as(ip)
-    s.cameras, s.n_dist = self.cameras.ctypes.data_as(dp), self.n_dist
-    s.camera_n_dist, s.is_fisheye = self.camera_n_dist.ctypes.data_as(ip), self.is_fisheye.ctypes.data_as(up)
+    s.points, s.valid = dp(self.points), up(self.valid)
+    s.board_points, s.board_sizes = dp(self.board_points), ip(self.board_sizes)
+    s.cameras, s.n_dist = dp(self.cameras), self.n_dist
+    s.camera_n_dist, s.is_fisheye = ip(self.camera_n_dist), up(self.is_fisheye)
     s.fix_aspect = None
-    s.view_mask = None if self.view_mask is None else self.view_mask.ctypes.data_as(up)
-    s.init_poses = None if self.init_poses is None else self.init_poses.ctypes.data_as(dp)
+    s.view_mask = up(self.view_mask)
+    s.init_poses = dp(self.init_poses)
     s.max_iterations = self.max_iterations
-    s.lm_iterations = self.lm_iterations.ctypes.data_as(ip)
+    s.lm_iterations = ip(self.lm_iterations)
     return s
 
   def outputs(self):
@@ -393,9 +379,7 @@ def view_poses(points, valid, board_points, cameras, view_mask=None, init_poses=
   inp = ViewPoseInputs(points, valid, board_points, cameras, view_mask, init_poses, max_iterations)
   poses, sse, n_used, status = inp.outputs()
   s = inp.struct()
-  dp = C.POINTER(C.c_double)
-  check(_lib.load().mcba_view_poses(C.byref(s), poses.ctypes.data_as(dp), sse.ctypes.data_as(dp),
-                                    n_used.ctypes.data_as(C.POINTER(C.c_int32)), status.ctypes.data_as(C.POINTER(C.c_uint8))))
+  check(_lib.load().mcba_view_poses(C.byref(s), dp(poses), dp(sse), ip(n_used), up(status)))
   return poses, sse, n_used, status, inp.lm_iterations
 
 
@@ -538,20 +522,19 @@ class IntrinsicInputs(object):
     self.lm_iterations = np.zeros(C_, dtype=np.int32)
 
   def struct(self):
-    dp, up, ip = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
     s = _lib.IntrinsicProblem()
     s.C, s.F, s.B = self.shape
     s.P = self.valid.shape[3]
-    s.points, s.valid = self.points.ctypes.data_as(dp), self.valid.ctypes.data_as(up)
-    s.board_points, s.board_sizes = self.board_points.ctypes.data_as(dp), self.board_sizes.ctypes.data_as(ip)
-    s.image_sizes, s.n_dist = self.image_sizes.ctypes.data_as(dp), self.n_dist
-    s.camera_n_dist, s.is_fisheye = self.camera_n_dist.ctypes.data_as(ip), self.is_fisheye.ctypes.data_as(up)
-    s.fix_aspect, s.free_dist = self.fix_aspect.ctypes.data_as(up), self.free_dist.ctypes.data_as(up)
-    s.view_mask = None if self.view_mask is None else self.view_mask.ctypes.data_as(up)
-    s.init_cameras = None if self.init_cameras is None else self.init_cameras.ctypes.data_as(dp)
-    s.init_poses = None if self.init_poses is None else self.init_poses.ctypes.data_as(dp)
+    s.points, s.valid = dp(self.points), up(self.valid)
+    s.board_points, s.board_sizes = dp(self.board_points), ip(self.board_sizes)
+    s.image_sizes, s.n_dist = dp(self.image_sizes), self.n_dist
+    s.camera_n_dist, s.is_fisheye = ip(self.camera_n_dist), up(self.is_fisheye)
+    s.fix_aspect, s.free_dist = up(self.fix_aspect), up(self.free_dist)
+    s.view_mask = up(self.view_mask)
+    s.init_cameras = dp(self.init_cameras)
+    s.init_poses = dp(self.init_poses)
     s.max_iterations = self.max_iterations
-    s.lm_iterations = self.lm_iterations.ctypes.data_as(ip)
+    s.lm_iterations = ip(self.lm_iterations)
     return s
 
   def call(self, fn, *extra):
@@ -559,10 +542,8 @@ class IntrinsicInputs(object):
     C_ = self.shape[0]
     cameras, poses, sse = np.zeros((C_, 5 + self.n_dist)), np.empty(self.shape + (4, 4)), np.empty(self.shape)
     n_used, vstat, cstat = np.empty(self.shape, dtype=np.int32), np.empty(self.shape, dtype=np.uint8), np.empty(C_, dtype=np.uint8)
-    dp, up, ip = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
     s = self.struct()
-    rc = fn(C.byref(s), cameras.ctypes.data_as(dp), poses.ctypes.data_as(dp), sse.ctypes.data_as(dp), n_used.ctypes.data_as(ip),
-            vstat.ctypes.data_as(up), cstat.ctypes.data_as(up), *extra)
+    rc = fn(C.byref(s), dp(cameras), dp(poses), dp(sse), ip(n_used), up(vstat), up(cstat), *extra)
     n_cam, sse_cam = n_used.reshape(C_, -1).sum(axis=1), sse.reshape(C_, -1).sum(axis=1)
     return rc, struct(cameras=cameras, camera_n_dist=self.camera_n_dist.copy(), poses=poses, sse=sse, n_used=n_used,
                       view_status=vstat, camera_status=cstat, lm_iterations=self.lm_iterations,

@@ -13,30 +13,13 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import dp as _dp, entry as _entry, f64 as _f64, ip as _ip, u8 as _u8, up as _up   # noqa: F401 (_entry: see _lib.entry)
 from .structs import struct
-from .undistort import CameraSetInputs, _dp, _f64
+from .undistort import CameraSetInputs
 
 OK, TOO_FEW, DEGENERATE, NOT_CONVERGED, BEHIND = (_lib.TRI_OK, _lib.TRI_TOO_FEW, _lib.TRI_DEGENERATE, _lib.TRI_NOT_CONVERGED,
                                                   _lib.TRI_BEHIND)
 MAX_CAMERAS = _lib.TRI_MAX_CAMERAS
-
-
-def _entry(name):
-  """The library function behind a wrapper: raises with the library's message.  (The host tests put the g++ build of the same
-  header here.)"""
-  fn = getattr(_lib.load(), "mcba_" + name)
-  return lambda *args: check(fn(*args))
-
-
-def _u8(a, shape, what):
-  a = np.ascontiguousarray(np.asarray(a).astype(np.uint8))
-  assert a.shape == shape, f"{what} is {a.shape}, not {shape}"
-  return a
-
-
-def _up(a):
-  return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
 
 
 def _views(views, n_cameras, what):
@@ -80,7 +63,7 @@ def triangulate(cameras, views, points, valid, views_end=None, view_valid=None, 
   p.view_valid, p.points, p.valid = _up(view_valid), _dp(points), _up(valid)
   p.sigma_px = 0.0 if sigma is None else float(sigma)
   p.max_iterations = int(max_iterations)
-  _entry("triangulate")(C.byref(p), _dp(X), _dp(cov), _dp(sse), _dp(err), n_views.ctypes.data_as(C.POINTER(C.c_int32)), _up(status))
+  _entry("triangulate")(C.byref(p), _dp(X), _dp(cov), _dp(sse), _dp(err), _ip(n_views), _up(status))
   return struct(points=X, cov=covariance_matrices(cov), sse=sse, error=err, n_views=n_views, status=status)
 
 
@@ -100,6 +83,4 @@ def triangulate_rig(cameras, camera_poses, rig_poses, points, valid, rig_poses_e
 
 def last_call_ms():
   """mcba_debug_triangulate_ms of this thread's last call: (dict(upload, kernel, download, call) in milliseconds, points launched)."""
-  ms, n = np.zeros(4), C.c_int64(0)
-  check(_lib.load().mcba_debug_triangulate_ms(_dp(ms), C.byref(n)))
-  return dict(upload=ms[0], kernel=ms[1], download=ms[2], call=ms[3]), int(n.value)
+  return _lib.call_ms("triangulate", ("upload", "kernel", "download", "call"))

@@ -14,30 +14,11 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import dp as _dp, entry as _entry, f64 as _f64, fp as _fp, ip as _ip, up as _up   # noqa: F401 (_entry: see _lib.entry)
 from .tables import _is_fisheye
 
 UNDISTORT_OK, UNDISTORT_NOT_CONVERGED = _lib.UNDISTORT_OK, _lib.UNDISTORT_NOT_CONVERGED
 _DTYPES = {np.dtype(np.uint8): _lib.PIXEL_U8, np.dtype(np.float32): _lib.PIXEL_F32}
-
-
-def _entry(name):
-  """The library function behind a wrapper: raises with the library's message.  (The host tests put the g++ build of the same
-  header here.)"""
-  fn = getattr(_lib.load(), "mcba_" + name)
-  return lambda *args: check(fn(*args))
-
-
-def _f64(a):
-  return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
-
-
-def _dp(a):
-  return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _ip(a):
-  return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 class CameraSetInputs(object):
@@ -71,7 +52,7 @@ class CameraSetInputs(object):
     s = _lib.CameraSet()
     s.C, s.cameras, s.n_dist = self.n, _dp(self.cameras), self.n_dist
     s.camera_n_dist = _ip(self.camera_n_dist)
-    s.is_fisheye = self.is_fisheye.ctypes.data_as(C.POINTER(C.c_uint8))
+    s.is_fisheye = _up(self.is_fisheye)
     return s
 
   def index(self, of, n):
@@ -126,7 +107,7 @@ def undistort_points(cameras, pixels, camera_of_point=None, R=None, P=None):
   out, status = np.empty((len(uv), 2)), np.empty(len(uv), dtype=np.uint8)
   s = inp.struct()
   _entry("undistort_points")(C.byref(s), len(uv), _ip(of), _dp(uv), _dp(inp.R), _dp(inp.P), _dp(out),
-                             status.ctypes.data_as(C.POINTER(C.c_uint8)))
+                             _up(status))
   return out, status
 
 
@@ -137,7 +118,7 @@ def undistort_maps(cameras, image_size, R=None, P=None):
   w, h = int(image_size[0]), int(image_size[1])
   maps = np.empty((inp.n, h, w, 2), dtype=np.float32)
   s = inp.struct()
-  _entry("undistort_maps")(C.byref(s), _dp(inp.R), _dp(inp.P), w, h, maps.ctypes.data_as(C.POINTER(C.c_float)))
+  _entry("undistort_maps")(C.byref(s), _dp(inp.R), _dp(inp.P), w, h, _fp(maps))
   return maps
 
 
@@ -153,7 +134,7 @@ def remap(images, maps, map_of_image=None, border=0.0):
   M, hd, wd = maps.shape[:3]
   out = batch.output(hd, wd)
   _entry("remap")(batch.data.ctypes.data_as(C.c_void_p), batch.n, batch.h, batch.w, batch.channels, batch.dtype,
-                  maps.ctypes.data_as(C.POINTER(C.c_float)), M, hd, wd, _ip(of), float(border), out.ctypes.data_as(C.c_void_p))
+                  _fp(maps), M, hd, wd, _ip(of), float(border), out.ctypes.data_as(C.c_void_p))
   return batch.shaped(out)
 
 
@@ -173,6 +154,4 @@ def undistort_images(cameras, images, camera_of_image=None, image_size=None, R=N
 
 def last_call_ms():
   """mcba_debug_undistort_ms of this thread's last call: (dict(upload, kernel, download, call) in milliseconds, pixels written)."""
-  ms, n = np.zeros(4), C.c_int64(0)
-  check(_lib.load().mcba_debug_undistort_ms(_dp(ms), C.byref(n)))
-  return dict(upload=ms[0], kernel=ms[1], download=ms[2], call=ms[3]), int(n.value)
+  return _lib.call_ms("undistort", ("upload", "kernel", "download", "call"))

@@ -6,7 +6,6 @@ of 5 calls after 2 warm-up calls) and the problem count; the time of the g++ bui
     python profiles/scripts/prof_hand_eye.py --device      # needs the GPU
     python profiles/scripts/prof_hand_eye.py --host        # host build + restatement, no GPU
 """
-import ctypes as C
 import os
 import sys
 import time
@@ -20,9 +19,8 @@ from multical_amd import synthetic, tables, _lib   # noqa: E402
 
 
 def breakdown():
-  ms, n = (C.c_double * 4)(), C.c_int64()
-  _lib.check(_lib.load().mcba_debug_hand_eye_ms(ms, C.byref(n)))
-  return np.array(list(ms)), n.value
+  ms, n = _lib.call_ms("hand_eye", range(4))
+  return np.array(list(ms.values())), n
 
 
 def main(device, host):

@@ -7,7 +7,6 @@ scaled to the rig).
     python profiles/scripts/prof_intrinsics.py --device      # needs the GPU
     python profiles/scripts/prof_intrinsics.py --host        # host build + restatement, no GPU
 """
-import ctypes as C
 import os
 import sys
 import time
@@ -37,9 +36,8 @@ def make(label, cfg):
 
 
 def breakdown():
-  ms, n = (C.c_double * 4)(), C.c_int64()
-  _lib.check(_lib.load().mcba_debug_calibrate_intrinsics_ms(ms, C.byref(n)))
-  return np.array(list(ms)), n.value
+  ms, n = _lib.call_ms("calibrate_intrinsics", range(4))
+  return np.array(list(ms.values())), n
 
 
 def main(device, host):

@@ -7,7 +7,6 @@ Newton undistortion + scipy least_squares) per view on one core beside it.  Medi
     python profiles/scripts/prof_pose_table.py cfg3 --kernel          # + k_view_pose under rocprofv3 --kernel-trace --stats
     python profiles/scripts/prof_pose_table.py cfg3 --calls-only      # (what the --kernel child runs)
 """
-import ctypes as C
 import csv
 import glob
 import os
@@ -25,9 +24,8 @@ from multical_amd import synthetic, tables, _lib   # noqa: E402
 
 
 def breakdown():
-  ms, n = (C.c_double * 4)(), C.c_int64()
-  _lib.check(_lib.load().mcba_debug_view_poses_ms(ms, C.byref(n)))
-  return np.array(list(ms)), n.value
+  ms, n = _lib.call_ms("view_poses", range(4))
+  return np.array(list(ms.values())), n
 
 
 def main(cfg, calls_only=False, kernel=False):

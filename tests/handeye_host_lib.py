@@ -11,22 +11,9 @@ from multical_amd import _lib, tables
 import pnp_host_lib
 
 
-def build(force=False):
-  return host_build.build("handeye_host", "handeye_host.cpp", host_build.IEEE, force)
-
-
-_h = None
-
-
-def lib():
-  global _h
-  if _h is None:
-    build()
-    _h = host_build.load("handeye_host", "he")
-    dp = C.POINTER(C.c_double)
-    _h.he_hand_eye.restype = C.c_int32
-    _h.he_hand_eye.argtypes = [C.POINTER(_lib.HandEyeProblem), dp, dp, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), dp, C.c_int32]
-  return _h
+_host = host_build.HostLib("handeye_host", "he", extra=dict(
+    hand_eye=[C.POINTER(_lib.HandEyeProblem), _lib.c_double_p, _lib.c_double_p, _lib.c_int32_p, _lib.c_uint8_p, _lib.c_double_p, C.c_int32]))
+lib, build = _host.lib, _host.build
 
 
 def hand_eye_batch(table_a, valid_a, table_b, valid_b, index_a, index_b, invert=False, reversed_order=False):
@@ -34,11 +21,8 @@ def hand_eye_batch(table_a, valid_a, table_b, valid_b, index_a, index_b, invert=
   inp = tables.HandEyeInputs(table_a, valid_a, table_b, valid_b, index_a, index_b, invert)
   X, Z, n_pairs, status, err = inp.outputs()
   s = inp.struct()
-  dp = C.POINTER(C.c_double)
-  rc = lib().he_hand_eye(C.byref(s), X.ctypes.data_as(dp), Z.ctypes.data_as(dp), n_pairs.ctypes.data_as(C.POINTER(C.c_int32)),
-                         status.ctypes.data_as(C.POINTER(C.c_uint8)), err.ctypes.data_as(dp), 1 if reversed_order else 0)
-  if rc != 0:
-    raise RuntimeError(lib().he_last_error().decode())
+  _host.check(lib().he_hand_eye(C.byref(s), _lib.dp(X), _lib.dp(Z), _lib.ip(n_pairs), _lib.up(status), _lib.dp(err),
+                                1 if reversed_order else 0))
   return X, Z, n_pairs, status, err
 
 

@@ -8,24 +8,8 @@ from multical_amd import _lib
 from multical_amd.backend import lower, _to_struct, _ptr, _f64
 
 
-def build(force=False):
-  return host_build.build("hostmath", "hostmath.cpp", ["-pthread"], force)
-
-
-_h = None
-
-
-def lib():
-  global _h
-  if _h is None:
-    build()
-    _h = host_build.load("hostmath", "hm")
-  return _h
-
-
-def _check(rc):
-  if rc != 0:
-    raise RuntimeError(lib().hm_last_error().decode())
+_host = host_build.HostLib("hostmath", "hm", flags=["-pthread"])
+lib, build, _check = _host.lib, _host.build, _host.check
 
 
 class HostMath(object):

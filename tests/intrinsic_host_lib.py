@@ -9,22 +9,10 @@ from multical_amd import _lib, synthetic, tables
 from multical_amd.structs import struct
 
 
-def build(force=False):
-  return host_build.build("intrinsic_host", "intrinsic_host.cpp", host_build.IEEE, force)
-
-
-_h = None
-
-
-def lib():
-  global _h
-  if _h is None:
-    build()
-    _h = host_build.load("intrinsic_host", "intrinsic")
-    dp, up, ip = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
-    _h.intrinsic_calibrate.restype = C.c_int32
-    _h.intrinsic_calibrate.argtypes = [C.POINTER(_lib.IntrinsicProblem), dp, dp, dp, ip, up, up, C.c_int32]
-  return _h
+_host = host_build.HostLib("intrinsic_host", "intrinsic", extra=dict(
+    calibrate=[C.POINTER(_lib.IntrinsicProblem), _lib.c_double_p, _lib.c_double_p, _lib.c_double_p, _lib.c_int32_p, _lib.c_uint8_p,
+               _lib.c_uint8_p, C.c_int32]))
+lib, build = _host.lib, _host.build
 
 
 def calibrate_intrinsics(point_table, boards, image_sizes, model='standard', fix_aspect=False, view_mask=None, init=None,
@@ -37,8 +25,7 @@ def calibrate_intrinsics(point_table, boards, image_sizes, model='standard', fix
   inp = tables.IntrinsicInputs(point_table.points, valid, boards_pts, image_sizes, model, fix_aspect, view_mask, init, free_dist,
                                max_iterations)
   rc, out = inp.call(lib().intrinsic_calibrate, 1 if device_order else 0)
-  if rc != 0:
-    raise RuntimeError(lib().intrinsic_last_error().decode())
+  _host.check(rc)
   return out
 
 

@@ -4,7 +4,6 @@ mcba_rig_poses) + the rigs the localisation tests share.
 The rigs come from multical_amd.synthetic.make_rig with a configuration of their own (cameras x boards x camera model x motion), at
 the TRUTH calibration: localisation holds everything but the frames' poses, so a noise-free table has its optimum at the truth.
 """
-import contextlib
 import ctypes as C
 from types import SimpleNamespace
 
@@ -32,50 +31,9 @@ RIGS = {
 RIG_IDS = list(RIGS)
 
 
-def build(force=False):
-  return host_build.build("localize_host", "localize_host.cpp", host_build.IEEE, force)
-
-
-_h = None
-
-
-def lib():
-  global _h
-  if _h is None:
-    build()
-    _h = host_build.load("localize_host", "lh")
-    signatures = {name: (restype, argtypes) for name, restype, argtypes in _lib.SYMBOLS}
-    _h.lh_rig_poses.restype, _h.lh_rig_poses.argtypes = signatures["mcba_rig_poses"]
-    dp = C.POINTER(C.c_double)
-    _h.lh_score_candidates.restype = C.c_int32
-    _h.lh_score_candidates.argtypes = [C.POINTER(_lib.RigPoseProblem), C.c_int32, C.c_int32, dp, dp, C.POINTER(C.c_int32)]
-  return _h
-
-
-def entry(name):
-  """localize._entry of the host build"""
-  fn = getattr(lib(), "lh_" + name)
-
-  def call(*args):
-    if fn(*args) != 0:
-      raise RuntimeError(lib().lh_last_error().decode())
-  return call
-
-
-@contextlib.contextmanager
-def host_backend():
-  """multical_amd.localize (and what sits on it: Calibration.localize, with_localized_frames) served by the host build"""
-  saved = localize._entry
-  localize._entry = entry
-  try:
-    yield localize
-  finally:
-    localize._entry = saved
-
-
-def on_host(fn, *args, **kwargs):
-  with host_backend():
-    return fn(*args, **kwargs)
+_host = host_build.HostLib("localize_host", "lh", ["rig_poses"], module=localize, extra=dict(
+    score_candidates=[C.POINTER(_lib.RigPoseProblem), C.c_int32, C.c_int32, _lib.c_double_p, _lib.c_double_p, _lib.c_int32_p]))
+lib, build, entry, host_backend, on_host = _host.lib, _host.build, _host.entry, _host.host_backend, _host.on_host
 
 
 # ---- rigs ------------------------------------------------------------------------------------------------------------------
@@ -237,9 +195,7 @@ def raw_problem(rig, n_cameras=None, **kwargs):
 
 def raw_call(fn, p, out, full=False):
   """rc of fn(problem, poses, ..., status): every optional output NULL unless full"""
-  from multical_amd.undistort import _dp
-  i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-  u8 = out.status.ctypes.data_as(C.POINTER(C.c_uint8))
+  _dp, i32, u8 = _lib.dp, _lib.ip, _lib.up(out.status)
   if full:
     return fn(C.byref(p), _dp(out.poses), _dp(out.poses_end), _dp(out.cov), _dp(out.sse), i32(out.n_obs), i32(out.iters), _dp(out.error), u8)
   return fn(C.byref(p), _dp(out.poses), None, None, None, None, None, None, u8)
@@ -247,10 +203,8 @@ def raw_call(fn, p, out, full=False):
 
 def score_candidates(rig, f, candidates):
   """(scores [n], picked) of the header's scoring step for frame f"""
-  from multical_amd.undistort import _dp
   p, _, keep = raw_problem(rig)
   cand = np.ascontiguousarray(np.asarray(candidates, dtype=np.float64).reshape(-1, 4, 4))
   scores, picked = np.zeros(len(cand)), C.c_int32(-1)
-  if lib().lh_score_candidates(C.byref(p), f, len(cand), _dp(cand), _dp(scores), C.byref(picked)) != 0:
-    raise RuntimeError(lib().lh_last_error().decode())
+  _host.check(lib().lh_score_candidates(C.byref(p), f, len(cand), _lib.dp(cand), _lib.dp(scores), C.byref(picked)))
   return scores, int(picked.value)

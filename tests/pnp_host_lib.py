@@ -11,25 +11,10 @@ from multical_amd import _lib, synthetic, tables
 HERE = host_build.HERE
 
 
-def build(force=False):
-  return host_build.build("pnp_host", "pnp_host.cpp", host_build.IEEE, force)
-
-
-_h = None
-
-
-def lib():
-  global _h
-  if _h is None:
-    build()
-    _h = host_build.load("pnp_host", "pnp")
-    _h.pnp_view_poses.restype = C.c_int32
-    _h.pnp_view_poses.argtypes = [C.POINTER(_lib.ViewPoseProblem), C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                  C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int32]
-    _h.pnp_undistort.restype = C.c_int32
-    _h.pnp_undistort.argtypes = [C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
-                                 C.POINTER(C.c_double)]
-  return _h
+_host = host_build.HostLib("pnp_host", "pnp", extra=dict(
+    view_poses=[C.POINTER(_lib.ViewPoseProblem), _lib.c_double_p, _lib.c_double_p, _lib.c_int32_p, _lib.c_uint8_p, C.c_int32],
+    undistort=[_lib.c_double_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _lib.c_double_p]))
+lib, build = _host.lib, _host.build
 
 
 def view_poses(points, valid, board_points, cameras, view_mask=None, init_poses=None, max_iterations=0, pairwise=False):
@@ -37,11 +22,7 @@ def view_poses(points, valid, board_points, cameras, view_mask=None, init_poses=
   inp = tables.ViewPoseInputs(points, valid, board_points, cameras, view_mask, init_poses, max_iterations)
   poses, sse, n_used, status = inp.outputs()
   s = inp.struct()
-  dp = C.POINTER(C.c_double)
-  rc = lib().pnp_view_poses(C.byref(s), poses.ctypes.data_as(dp), sse.ctypes.data_as(dp), n_used.ctypes.data_as(C.POINTER(C.c_int32)),
-                            status.ctypes.data_as(C.POINTER(C.c_uint8)), 1 if pairwise else 0)
-  if rc != 0:
-    raise RuntimeError(lib().pnp_last_error().decode())
+  _host.check(lib().pnp_view_poses(C.byref(s), _lib.dp(poses), _lib.dp(sse), _lib.ip(n_used), _lib.up(status), 1 if pairwise else 0))
   return poses, sse, n_used, status, inp.lm_iterations
 
 
@@ -53,8 +34,7 @@ def undistort(camera, uv):
   out, ok = np.zeros((len(uv), 2)), np.zeros(len(uv), dtype=bool)
   xy = (C.c_double * 2)()
   for i, (u, v) in enumerate(np.asarray(uv, dtype=np.float64)):
-    ok[i] = lib().pnp_undistort(block.ctypes.data_as(C.POINTER(C.c_double)), int(np.asarray(camera.dist).size), fish, 0,
-                                float(u), float(v), xy) != 0
+    ok[i] = lib().pnp_undistort(_lib.dp(block), int(np.asarray(camera.dist).size), fish, 0, float(u), float(v), xy) != 0
     out[i] = xy[0], xy[1]
   return out, ok
 

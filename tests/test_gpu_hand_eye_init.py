@@ -76,9 +76,8 @@ def test_device_matches_host_build_on_the_noisy_chain_of_cfg5_40():
 
 
 def _timing():
-  ms, n = (C.c_double * 4)(), C.c_int64(-1)
-  _lib.check(_lib.load().mcba_debug_hand_eye_ms(ms, C.byref(n)))
-  return list(ms), n.value
+  ms, n = _lib.call_ms("hand_eye", range(4))
+  return list(ms.values()), n
 
 
 def test_empty_launches():

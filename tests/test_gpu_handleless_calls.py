@@ -1,9 +1,9 @@
-"""The five handle-less entry families (pose alignment, pose table, intrinsics, hand-eye start, undistortion) share one call
-scaffold (csrc/mcba_host.h: DeviceCall) and one resource cache: streams and buffers parked by one family are taken by the next.
-One process, one thread: every family twice, interleaved A B C D E A B C D E, at the smallest shapes -- the second result of each
-is the first byte for byte, every family's timing count is its own, and a call refused at argument checking leaves that family's
-message in mcba_last_error() and the next valid call returns the bytes it returned before.  (Every refusal here comes before the
-call takes its stream: argument errors only, so the parking of a call that fails on the device is not exercised.)"""
+"""The seven handle-less entry families (pose alignment, pose table, intrinsics, hand-eye start, undistortion, triangulation, rig
+localisation) share one call scaffold (csrc/mcba_host.h: DeviceCall) and one resource cache: streams and buffers parked by one family
+are taken by the next.  One process, one thread: every family twice, interleaved A .. G A .. G, at the smallest shapes -- the second
+result of each is the first byte for byte, every family's timing count is its own, and a call refused at argument checking leaves
+that family's message in mcba_last_error() and the next valid call returns the bytes it returned before.  (Every refusal here comes
+before the call takes its stream: argument errors only, so the parking of a call that fails on the device is not exercised.)"""
 import ctypes as C
 
 import numpy as np
@@ -11,9 +11,11 @@ import pytest
 
 import handeye_host_lib as hh
 import intrinsic_host_lib as I
+import localize_host_lib as lh
 import pnp_host_lib as L
+import triangulate_host_lib as th
 import undistort_host_lib as uh
-from multical_amd import _lib, synthetic, tables, undistort
+from multical_amd import _lib, localize, synthetic, tables, triangulate, undistort
 
 pytestmark = pytest.mark.gpu
 
@@ -31,10 +33,8 @@ def _alignment_problems():
   return problems
 
 
-def _count(getter):
-  ms, n = (C.c_double * 4)(), C.c_int64(-1)
-  _lib.check(getattr(_lib.load(), getter)(ms, C.byref(n)))
-  return n.value
+def _count(getter, slots=4):
+  return _lib.call_ms(getter, range(slots))[1]
 
 
 def _bytes(arrays):
@@ -45,7 +45,7 @@ def _last_error():
   return _lib.load().mcba_last_error().decode()
 
 
-def test_five_families_interleaved_through_one_cache():
+def test_seven_families_interleaved_through_one_cache():
   rig = L.golden_rig("tiny")
   irig = I.rig("tiny")
   ta, va, tb, vb, _, _ = hh.interleaved_problem(5, 6, n_rows=2)
@@ -54,6 +54,8 @@ def test_five_families_interleaved_through_one_cache():
   X = np.concatenate([rng.uniform(-0.3, 0.3, (1000, 2)), rng.uniform(1.0, 2.0, (1000, 1))], axis=1)
   of = rng.integers(0, len(CAMERAS), 1000).astype(np.int32)
   image = uh.noise_image(5, (1, uh.IMAGE_SIZE[1], uh.IMAGE_SIZE[0]), np.uint8)
+  trig = th.make_rig(2, 1, 65)                        # (65 points: across one 64-lane edge)
+  lrig = lh.named_rig("1cam-2board-pin5-rolling")     # (4 frames)
 
   def align():
     out, valid, inliers = tables.align_transforms_robust_batch(problems)
@@ -73,7 +75,15 @@ def test_five_families_interleaved_through_one_cache():
     uv = undistort.project_points(CAMERAS, X, of)
     return _bytes([uv, undistort.undistort_images(CAMERAS, image, [0], image_size=(57, 5))])
 
-  families = [align, view_poses, intrinsics, hand_eye, undistortion]
+  def triangulation():
+    r = th.run(trig, "device")
+    return _bytes(r[k] for k in ("points", "cov", "sse", "error", "n_views", "status"))
+
+  def localisation():
+    r = lh.run(lrig, "device")
+    return _bytes(r[k] for k in ("poses", "poses_end", "cov", "sse", "n_obs", "iters", "error", "status"))
+
+  families = [align, view_poses, intrinsics, hand_eye, undistortion, triangulation, localisation]
   first = [f() for f in families]
   second = [f() for f in families]
   for f, a, b in zip(families, first, second):
@@ -85,12 +95,14 @@ def test_five_families_interleaved_through_one_cache():
   assert np.all(out.camera_status == tables.CAMERA_OK)
   idle = (tables.VIEW_MASKED, tables.VIEW_TOO_FEW)
   counts = dict(view_poses=int((~np.isin(status, idle)).sum()), intrinsics=int((~np.isin(out.view_status, idle)).sum()),
-                hand_eye=2, undistortion=57 * 5)
-  assert len(set(counts.values())) == 4, counts          # (shapes chosen so that a mixed-up count shows)
+                hand_eye=2, undistortion=57 * 5, triangulation=65, localisation=4)
+  assert len(set(counts.values())) == 6, counts          # (shapes chosen so that a mixed-up count shows)
   hand_eye()
   undistortion()
-  got = dict(view_poses=_count("mcba_debug_view_poses_ms"), intrinsics=_count("mcba_debug_calibrate_intrinsics_ms"),
-             hand_eye=_count("mcba_debug_hand_eye_ms"), undistortion=_count("mcba_debug_undistort_ms"))
+  triangulation()
+  localisation()
+  got = dict(view_poses=_count("view_poses"), intrinsics=_count("calibrate_intrinsics"), hand_eye=_count("hand_eye"),
+             undistortion=_count("undistort"), triangulation=_count("triangulate"), localisation=_count("rig_poses", 5))
   assert got == counts
 
   # refused at argument checking: the family's own message, and the next valid call returns the bytes it returned before
@@ -98,6 +110,14 @@ def test_five_families_interleaved_through_one_cache():
   bumpy[::3, 2] += 0.005
   ibumpy = np.asarray(irig.board_points[0], dtype=np.float64).copy()
   ibumpy[::3, 2] += 0.005
+  def null_points():           # (the raw call: the wrapper never leaves X out)
+    p, out, keep = th.raw_problem(trig)
+    _lib.check(_lib.load().mcba_triangulate(C.byref(p), None, None, None, None, None, _lib.up(out["status"])))
+
+  def too_many_cameras():
+    p, out, keep = lh.raw_problem(lrig, n_cameras=localize.MAX_CAMERAS + 1)
+    _lib.check(lh.raw_call(_lib.load().mcba_rig_poses, p, out))
+
   refused = [
       (lambda: tables.align_transforms_robust_indexed(problems[2][0], np.full(200, 200), np.zeros(200, dtype=np.int64),
                                                       np.array([9, 30, 161])), "pose index out of range"),
@@ -108,6 +128,8 @@ def test_five_families_interleaved_through_one_cache():
       (lambda: tables.hand_eye_batch(ta, va, tb, vb, [0, 2], [0, 1]), "mcba_hand_eye: problem 1: rows (2, 1) outside tables of 2 and 2 rows"),
       (lambda: undistort.remap(np.zeros((1, 4, 4, 2), dtype=np.uint8), np.zeros((4, 4, 2), dtype=np.float32)),
        "mcba_remap: images of 1 or 3 channels are served, not 2"),
+      (null_points, "mcba_triangulate: null argument"),
+      (too_many_cameras, "mcba_rig_poses: 65 cameras, at most 64 are served"),
   ]
   for (call, message), family, before in zip(refused, families, first):
     with pytest.raises(RuntimeError) as e:

@@ -6,7 +6,6 @@ Shapes: 16-frame rigs give 6 .. 22 views per camera (above, below and not a mult
 81-corner boards are one full 64-corner chunk plus a partial one; tiny_mixed and tiny_fishmix launch once per (coefficients,
 fisheye) family; tiny_bigboard has 816 corners (13 chunks) next to an 81-corner board; masks leave a camera with 3 views (idle
 waves), one with a single view and one with none."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -90,9 +89,8 @@ def test_warm_start_at_the_optimum():
 
 
 def call_times():
-  ms, n = (C.c_double * 4)(), C.c_int64(-1)
-  _lib.check(_lib.load().mcba_debug_calibrate_intrinsics_ms(ms, C.byref(n)))
-  return list(ms), n.value
+  ms, n = _lib.call_ms("calibrate_intrinsics", range(4))
+  return list(ms.values()), n
 
 
 def test_nothing_active_touches_nothing():

@@ -7,7 +7,6 @@ import functools
 import logging
 import os
 import pickle
-import subprocess
 from types import SimpleNamespace
 
 import numpy as np
@@ -15,6 +14,7 @@ import pytest
 
 from multical_amd import localize
 
+import host_build
 import localize_host_lib as lh
 import localize_reference as lr
 
@@ -277,11 +277,7 @@ def test_a_masked_board_point_does_not_enter_the_plane_of_the_start():
 def test_sanitized_stand_alone_run(tmp_path):
   """the host build inside a small program of its own under AddressSanitizer + UBSan (CPU only): exact-size heap tables, pixels that
   are not finite, frames without observations, optional outputs left out -- no record is read and no error stored out of bounds"""
-  exe = str(tmp_path / "localize_sanitize")
-  src = os.path.join(lh.HERE, "localize_host", "localize_sanitize_main.cpp")
-  subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined,float-cast-overflow",
-                         "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-o", exe, src])
-  r = subprocess.run([exe], capture_output=True, text=True)
+  r = host_build.sanitized_program("localize_host", "localize_sanitize_main.cpp", tmp_path)
   assert r.returncode == 0 and "localize sanitize run: ok" in r.stdout, r.stdout + r.stderr
 
 

@@ -3,14 +3,13 @@ central-difference Jacobian (triangulate_reference.py), and the Python layer on 
 Calibration.triangulate / reconstruction_error) driven through that build.  No GPU."""
 import functools
 import logging
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from multical_amd import triangulate
 
+import host_build
 import triangulate_host_lib as th
 import triangulate_reference as tr
 import undistort_host_lib as uh
@@ -209,11 +208,7 @@ def test_sanitized_stand_alone_run(tmp_path):
   """the host build inside a small program of its own under AddressSanitizer + UBSan (CPU only): exact-size heap tables, pixels that
   are not finite or far outside every model, masked views, optional outputs left out -- no observation is read and no error stored
   out of bounds"""
-  exe = str(tmp_path / "triangulate_sanitize")
-  src = os.path.join(th.HERE, "triangulate_host", "triangulate_sanitize_main.cpp")
-  subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined,float-cast-overflow",
-                         "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-o", exe, src])
-  r = subprocess.run([exe], capture_output=True, text=True)
+  r = host_build.sanitized_program("triangulate_host", "triangulate_sanitize_main.cpp", tmp_path)
   assert r.returncode == 0 and "triangulate sanitize run: ok" in r.stdout, r.stdout + r.stderr
 
 

@@ -1,8 +1,6 @@
 """The undistortion mathematics (csrc/mcba_undistort.h) in its g++ build, against an independent numpy / scipy restatement
 (undistort_reference.py), and the Python layer on top of it driven through that build.  No GPU."""
-import os
 import pickle
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,6 +9,7 @@ from multical_amd import camera as camera_module
 from multical_amd import undistort
 from multical_amd.camera import Camera
 
+import host_build
 import undistort_host_lib as uh
 import undistort_reference as ref
 
@@ -189,11 +188,7 @@ def test_remap_refuses_what_it_does_not_serve():
 def test_sanitized_stand_alone_run(tmp_path):
   """the host build inside a small program of its own under AddressSanitizer + UBSan (CPU only): exact-size heap images, edge
   coordinates on both axes, every format -- no tap is read and no pixel stored out of bounds, no float -> int conversion overflows"""
-  exe = str(tmp_path / "undistort_sanitize")
-  src = os.path.join(uh.HERE, "undistort_host", "undistort_sanitize_main.cpp")
-  subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined,float-cast-overflow",
-                         "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-o", exe, src])
-  r = subprocess.run([exe], capture_output=True, text=True)
+  r = host_build.sanitized_program("undistort_host", "undistort_sanitize_main.cpp", tmp_path)
   assert r.returncode == 0 and "undistort sanitize run: ok" in r.stdout, r.stdout + r.stderr
 
 

@@ -9,8 +9,7 @@ Observations are projected through undistort_reference.project, the restated cv2
 multical_amd.synthetic._project to 3e-14 px, but synthetic._project has no tilt and lands 0.24 px away on the 14-coefficient camera,
 which would put a model error of five times the noise into every point that camera sees.
 """
-import contextlib
-
+import ctypes as C
 from types import SimpleNamespace
 
 import numpy as np
@@ -28,47 +27,8 @@ SHAPES = [(2, 1, 65, False), (3, 3, 65, False), (8, 2, 257, False), (8, 2, 130, 
 SHAPE_IDS = ["2x1x65", "3x3x65", "8x2x257", "8x2x130-rolling", "16x1x65"]
 
 
-def build(force=False):
-  return host_build.build("triangulate_host", "triangulate_host.cpp", host_build.IEEE, force)
-
-
-_h = None
-
-
-def lib():
-  global _h
-  if _h is None:
-    build()
-    _h = host_build.load("triangulate_host", "th")
-    signatures = {name: (restype, argtypes) for name, restype, argtypes in _lib.SYMBOLS}
-    _h.th_triangulate.restype, _h.th_triangulate.argtypes = signatures["mcba_triangulate"]
-  return _h
-
-
-def entry(name):
-  """triangulate._entry of the host build"""
-  fn = getattr(lib(), "th_" + name)
-
-  def call(*args):
-    if fn(*args) != 0:
-      raise RuntimeError(lib().th_last_error().decode())
-  return call
-
-
-@contextlib.contextmanager
-def host_backend():
-  """multical_amd.triangulate (and what sits on it: Calibration.triangulate, reconstruction_error) served by the host build"""
-  saved = triangulate._entry
-  triangulate._entry = entry
-  try:
-    yield triangulate
-  finally:
-    triangulate._entry = saved
-
-
-def on_host(fn, *args, **kwargs):
-  with host_backend():
-    return fn(*args, **kwargs)
+_host = host_build.HostLib("triangulate_host", "th", ["triangulate"], module=triangulate)
+lib, build, entry, host_backend, on_host = _host.lib, _host.build, _host.entry, _host.host_backend, _host.on_host
 
 
 # ---- the converging rig ----------------------------------------------------------------------------------------------------
@@ -155,8 +115,7 @@ def reference_problem(rig, points=None, **kwargs):
 def raw_problem(rig, n_cameras=None):
   """(mcba_triangulate_problem, outputs dict, keep-alive list) of the rig's table; n_cameras: claim that many cameras (the camera
   blocks are repeated; the table arrays are NOT grown -- only for calls that are refused before anything is read)"""
-  import ctypes as C
-  from multical_amd.undistort import CameraSetInputs, _dp
+  from multical_amd.undistort import CameraSetInputs
   cams = rig.cameras if n_cameras is None else [rig.cameras[c % len(rig.cameras)] for c in range(n_cameras)]
   inp = CameraSetInputs(cams)
   Cn, F, M = rig.shape
@@ -166,16 +125,14 @@ def raw_problem(rig, n_cameras=None):
   p = _lib.TriangulateProblem()
   p.cams = inp.struct()
   p.F, p.M = F, M
-  p.views, p.points, p.valid = _dp(views), _dp(points), valid.ctypes.data_as(C.POINTER(C.c_uint8))
+  p.views, p.points, p.valid = _lib.dp(views), _lib.dp(points), _lib.up(valid)
   p.sigma_px, p.max_iterations = 0.0, 20
   return p, out, [inp, views, points, valid]
 
 
 def raw_call(fn, p, out):
   """rc of fn(problem, X, NULL, NULL, NULL, NULL, status)"""
-  import ctypes as C
-  from multical_amd.undistort import _dp
-  return fn(C.byref(p), _dp(out["X"]), None, None, None, None, out["status"].ctypes.data_as(C.POINTER(C.c_uint8)))
+  return fn(C.byref(p), _lib.dp(out["X"]), None, None, None, None, _lib.up(out["status"]))
 
 
 # ---- calibrations of the golden rigs with noise-free detections ------------------------------------------------------------------

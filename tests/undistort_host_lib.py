@@ -1,11 +1,9 @@
 """TEST INFRASTRUCTURE: ctypes wrapper of tests/undistort_host (g++ build of multical_amd/csrc/mcba_undistort.h, the mathematics of
 the undistortion entry points) + the fixtures the undistortion tests share."""
-import contextlib
-
 import numpy as np
 
 import host_build
-from multical_amd import _lib, undistort
+from multical_amd import undistort
 from multical_amd.camera import Camera, CameraFisheye
 
 import pnp_host_lib
@@ -14,49 +12,8 @@ HERE = host_build.HERE
 NAMES = ["project_points", "undistort_points", "undistort_maps", "remap", "undistort_images"]
 
 
-def build(force=False):
-  return host_build.build("undistort_host", "undistort_host.cpp", host_build.IEEE, force)
-
-
-_h = None
-
-
-def lib():
-  global _h
-  if _h is None:
-    build()
-    _h = host_build.load("undistort_host", "uh")
-    signatures = {name: (restype, argtypes) for name, restype, argtypes in _lib.SYMBOLS}
-    for name in NAMES:
-      fn = getattr(_h, "uh_" + name)
-      fn.restype, fn.argtypes = signatures["mcba_" + name]
-  return _h
-
-
-def entry(name):
-  """undistort._entry of the host build"""
-  fn = getattr(lib(), "uh_" + name)
-
-  def call(*args):
-    if fn(*args) != 0:
-      raise RuntimeError(lib().uh_last_error().decode())
-  return call
-
-
-@contextlib.contextmanager
-def host_backend():
-  """multical_amd.undistort (and what sits on it: Camera.undistort_map, camera.undistort_images) served by the host build"""
-  saved = undistort._entry
-  undistort._entry = entry
-  try:
-    yield undistort
-  finally:
-    undistort._entry = saved
-
-
-def on_host(fn, *args, **kwargs):
-  with host_backend():
-    return fn(*args, **kwargs)
+_host = host_build.HostLib("undistort_host", "uh", NAMES, module=undistort)
+lib, build, entry, host_backend, on_host = _host.lib, _host.build, _host.entry, _host.host_backend, _host.on_host
 
 
 # ---- fixtures ------------------------------------------------------------------------------------------------------------
