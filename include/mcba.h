@@ -592,6 +592,44 @@ int32_t mcba_rig_poses(const mcba_rig_pose_problem* p, double* poses, double* po
  * [2] refinement kernel (both by HIP events), [3] downloads, [4] the whole call; *n_frames (or NULL) = frames launched       */
 int32_t mcba_debug_rig_poses_ms(double* ms /*[5]*/, int64_t* n_frames);
 
+/* --- using a calibration: projection uncertainty where no board was ------------------------------------------------- */
+/* The 2 x 2 covariance of where a point projects into camera b when the shared parameters vary with their covariance
+ * (csrc/mcba_uncertainty.h), for pixels anywhere in the image.  A job is one camera, one reference, one inverse
+ * distance and one factor W of the covariance; its queries are a grid generated on the device or a list of pixels.
+ *   reference < 0   the point n_b(q) / inv_distance is fixed in the rig frame; intrinsics and pose of `camera` vary: K = KI_b + 6
+ *   reference = a   camera a sees the point at pixel q at that distance; the result is the covariance of where `camera` sees it:
+ *                   K = KI_b + 6 + 6 + KI_a.  reference == camera returns exactly 0.
+ * KI_c = 4 + the camera's own coefficient count; n(q) the unit ray of the pixel through the exact inverse; inv_distance = 0: a
+ * direction.  W [K, r] row-major with W W^T = the covariance of the job's columns, in the order
+ *   fx fy cx cy dist.. of b | left perturbation (omega, tau) of camera_poses[b] | the same of a | fx fy cx cy dist.. of a
+ * (T -> exp(omega, tau) T; the caller folds d(omega, tau) / d(stored pose parameters) into W).  unconstrained [K] flags columns that
+ * no residual constrains and that are not held: a query whose row pair J has a non-zero entry there is MCBA_UNC_UNCONSTRAINED.
+ * C = (J W)(J W)^T.  Handle-less like mcba_view_poses; same error convention, the caller owns every array.                  */
+#define MCBA_UNC_MAX_K 48
+#define MCBA_UNC_OK 0
+#define MCBA_UNC_NOT_CONVERGED 1   /* the pixel (or where it lands in b) lies outside the monotone range of a model: NaN      */
+#define MCBA_UNC_BEHIND 2          /* transfer: the point lies at or behind the plane of camera b: NaN                        */
+#define MCBA_UNC_UNCONSTRAINED 3   /* J is non-zero on an unconstrained column: NaN                                           */
+typedef struct mcba_uncertainty_job {
+  int32_t camera, reference;     /* b; a or < 0 = the rig frame */
+  double inv_distance;           /* >= 0, finite */
+  int32_t K, r;                  /* rows and columns of W; r = 0 .. MCBA_UNC_MAX_K (0: C = 0) */
+  const double* W;               /* [K, r] */
+  const uint8_t* unconstrained;  /* [K] or NULL = none */
+  int32_t grid_w, grid_h;        /* grid_w > 0: grid_w x grid_h queries, row-major, query (ix, iy) = (u0 + ix du, v0 + iy dv) */
+  double u0, v0, du, dv;
+  int64_t n;                     /* grid_w == 0: n queries */
+  const double* uv;              /* [n,2] pixels */
+} mcba_uncertainty_job;
+/* Outputs, the jobs' queries one after the other (n_total of them): cov [n_total,3] (uu, uv, vv); std [n_total] or NULL = sqrt of
+ * the larger eigenvalue by the formula of mcba_observation_covariance (one rounding per operation); status [n_total] MCBA_UNC_*.
+ * camera_poses [C,4,4] rig -> camera.  Zero queries launch nothing.                                                          */
+int32_t mcba_projection_uncertainty(const mcba_camera_set* cams, const double* camera_poses, int32_t n_jobs,
+                                    const mcba_uncertainty_job* jobs, double* cov, double* std, uint8_t* status);
+/* timing of the last mcba_projection_uncertainty call of this thread, milliseconds: [0] uploads, [1] kernel (HIP events around the
+ * launch), [2] downloads, [3] the whole call; *n_queries (or NULL) = queries launched                                        */
+int32_t mcba_debug_projection_uncertainty_ms(double* ms /*[4]*/, int64_t* n_queries);
+
 /* --- solve -------------------------------------------------------------------------------------------------- */
 /* Trust-region least squares: replaces scipy.optimize.least_squares(method='trf', x_scale='jac', jac_sparsity=S,
  * loss, f_scale, ftol, max_nfev) at calibration.py:209-210.  x is updated in place to `res.x`.                 */

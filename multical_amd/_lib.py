@@ -97,10 +97,18 @@ class RigPoseProblem(C.Structure):   # mcba_rig_pose_problem
               ("image_heights", c_double_p), ("sigma_px", C.c_double), ("max_iterations", C.c_int32)]
 
 
+class UncertaintyJob(C.Structure):   # mcba_uncertainty_job
+  _fields_ = [("camera", C.c_int32), ("reference", C.c_int32), ("inv_distance", C.c_double), ("K", C.c_int32), ("r", C.c_int32),
+              ("W", c_double_p), ("unconstrained", c_uint8_p), ("grid_w", C.c_int32), ("grid_h", C.c_int32), ("u0", C.c_double),
+              ("v0", C.c_double), ("du", C.c_double), ("dv", C.c_double), ("n", C.c_int64), ("uv", c_double_p)]
+
+
 TRI_OK, TRI_TOO_FEW, TRI_DEGENERATE, TRI_NOT_CONVERGED, TRI_BEHIND = 0, 1, 2, 3, 4   # MCBA_TRI_*
 TRI_MAX_CAMERAS = 64                                  # MCBA_TRI_MAX_CAMERAS
 RIG_OK, RIG_TOO_FEW, RIG_DEGENERATE, RIG_NOT_CONVERGED, RIG_BEHIND = 0, 1, 2, 3, 4   # MCBA_RIG_*
 RIG_MAX_CAMERAS = 64                                  # MCBA_RIG_MAX_CAMERAS
+UNC_OK, UNC_NOT_CONVERGED, UNC_BEHIND, UNC_UNCONSTRAINED = 0, 1, 2, 3   # MCBA_UNC_*
+UNC_MAX_K = 48                                        # MCBA_UNC_MAX_K
 PIXEL_U8, PIXEL_F32 = 0, 1                            # MCBA_PIXEL_*
 UNDISTORT_OK, UNDISTORT_NOT_CONVERGED = 0, 1          # MCBA_UNDISTORT_*
 
@@ -156,6 +164,9 @@ SYMBOLS = [
   ("mcba_rig_poses", C.c_int32, [C.POINTER(RigPoseProblem), c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p,
                                  c_double_p, c_uint8_p]),
   ("mcba_debug_rig_poses_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_projection_uncertainty", C.c_int32, [C.POINTER(CameraSet), c_double_p, C.c_int32, C.POINTER(UncertaintyJob), c_double_p,
+                                              c_double_p, c_uint8_p]),
+  ("mcba_debug_projection_uncertainty_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_error_stats", C.c_int32, [H, c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), c_double_p,
                                    C.POINTER(C.c_int64), c_double_p]),
   ("mcba_error_count", C.c_int32, [H, C.c_int32, C.POINTER(C.c_int64)]),

@@ -744,6 +744,74 @@ class Calibration(parameters.Parameters):
          f"quantiles={stats.quantiles}, median translation std={med:.6f}")
     return r
 
+  # --- projection uncertainty where no board was ----------------------------------------------------
+  def _shared_layout(self):
+    """(camera_index, pose_index): per camera, where its stored block (fx fy cx cy skew dist..) and its pose (rvec | tvec) sit in
+    param_vec -- the layout split_std walks; None for a block that is not optimised"""
+    pos, out = 0, dict(cameras=None, camera_poses=None)
+    for k in ("camera_poses", "board_poses", "motion", "cameras", "boards"):
+      if self.optimize[k] is not True:
+        continue
+      if k == "camera_poses":
+        out[k] = [np.arange(pos + 6 * c, pos + 6 * c + 6) for c in range(self.size.cameras)]
+      elif k == "cameras":
+        at, out[k] = pos, []
+        for c in self.cameras:
+          n = np.asarray(c.param_vec).size
+          out[k].append(np.arange(at, at + n))
+          at += n
+      pos += parameters.count(self.params[k])
+    return out["cameras"], out["camera_poses"]
+
+  def projection_uncertainty(self, cameras=None, reference=None, distance=np.inf, grid=(16, 12), pixels=None, hold=None, sigma2=None):
+    """How far the calibration can be trusted anywhere in the image: the 2 x 2 covariance of where a point projects into each of
+    `cameras` (indices; None: all) when intrinsics and camera poses vary with `covariance(hold, sigma2)` (multical_amd.uncertainty,
+    one covariance and one device call).  reference=None: the point behind each pixel at `distance` is fixed in the rig frame -- with
+    the default hold that is the frame of the held camera, whose own map is then intrinsics-only; reference=a: camera a sees the
+    point at that pixel, the result is where each camera sees it (transfer / epipolar uncertainty, gauge-free; 0 for a itself).
+    grid=(gw, gh): centres u_i = (i + 0.5) W / gw - 0.5 (grid=image_size: every pixel); pixels [n, 2] with one camera: a list.
+    Returns struct(cov [C', gh, gw, 2, 2], std [C', gh, gw] (sqrt of the larger eigenvalue), pixels [C', gh, gw, 2], status
+    (uncertainty.OK / NOT_CONVERGED / BEHIND / UNCONSTRAINED; NaN where not OK), sigma2, dof)."""
+    from . import uncertainty
+    if self.optimize["boards"] is True:
+      raise ValueError("projection_uncertainty: not supported with the boards block optimised (the board points would join the "
+                       "shared system, as for prediction_covariance)")
+    return self._projection_uncertainty(self.covariance(hold=hold, sigma2=sigma2), cameras, reference, distance, grid, pixels)
+
+  def _projection_uncertainty(self, cov, cameras, reference, distance, grid, pixels):
+    from . import uncertainty
+    camera_index, pose_index = self._shared_layout()
+    rtvecs = np.asarray(self.camera_poses.params, dtype=np.float64).reshape(-1, 6)
+    out = uncertainty.projection_uncertainty(list(self.cameras), np.asarray(self.camera_poses.poses), cov, camera_index, pose_index,
+                                             query_cameras=cameras, reference=reference, distance=distance, grid=grid, pixels=pixels,
+                                             rtvecs=rtvecs)
+    return out._extend(sigma2=cov.sigma2, dof=cov.dof)
+
+  def report_projection_uncertainty(self, stage="", reference=None, distance=np.inf):
+    """One line per camera through the "calibration" logger: the standard deviation (px) of a projected point at the image centre,
+    its median and its worst value over the default 16 x 12 grid with the pixel where that occurs, and the share of grid cells
+    whose standard deviation is below the residual sigma."""
+    if self.optimize["boards"] is True:
+      raise ValueError("report_projection_uncertainty: not supported with the boards block optimised")
+    cov = self.covariance()
+    u = self._projection_uncertainty(cov, None, reference, distance, (16, 12), None)
+    sigma = float(np.sqrt(u.sigma2))
+    names = getattr(self.camera_poses, "names", None) or [f"cam{i}" for i in range(self.size.cameras)]
+    for c in range(self.size.cameras):
+      w, h = self.cameras[c].image_size
+      mid = self._projection_uncertainty(cov, [c], reference, distance, None, [[0.5 * (w - 1), 0.5 * (h - 1)]]).std[0]
+      std = u.std[c]
+      ok = np.isfinite(std)
+      if not ok.any():
+        info(f"{stage} {names[c]}: projection uncertainty not defined (no grid cell is constrained)")
+        continue
+      worst = np.unravel_index(np.nanargmax(std), std.shape)
+      at = u.pixels[c][worst]
+      info(f"{stage} {names[c]}: projected std centre={float(mid):.4f} median={float(np.median(std[ok])):.4f} "
+           f"max={float(std[worst]):.4f} px at ({at[0]:.0f}, {at[1]:.0f}), {100.0 * float((std[ok] < sigma).mean()):.0f}% of cells "
+           f"below sigma={sigma:.3f} px")
+    return u
+
 
 def split_std(calib, std):
   """A vector over calib.param_vec (standard deviations) split into the enabled blocks: camera_poses [C, 6], board_poses
