@@ -40,23 +40,27 @@ def _reference_columns(H, free, sigma2, cols):
   return out
 
 
-def _check_block(dev, ref, var_rows, var_cols, tol):
-  """|dSigma_ij| / sqrt(Sigma_ii Sigma_jj) <= tol; rows / columns with zero variance must be exactly zero."""
+def _check_block(dev, ref, var_rows, var_cols, tol, ratios=None):
+  """|dSigma_ij| / sqrt(Sigma_ii Sigma_jj) <= tol; rows / columns with zero variance must be exactly zero.  ratios (a list): receives
+  the largest error / tolerance ratio of the block."""
   scale = np.sqrt(np.outer(var_rows, var_cols))
   live = scale > 0
   assert np.all(dev[~live] == 0.0)
   if live.any():
     err = np.abs(dev - ref)[live] / scale[live]
+    if ratios is not None:
+      ratios.append(float(err.max()) / tol)
     assert err.max() <= tol, err.max()
 
 
-def _compare(h, x, hold, H, m, cost2, tol, frames=None, cross=True):
-  cov = h.covariance(x, hold=hold, cross=cross)
+def _compare(h, x, hold, H, m, cost2, tol, frames=None, cross=True, sigma2=None, ratios=None):
+  """sigma2: the residual variance handed to the device (None: the device's own estimate cost2 / dof, which is checked)"""
+  cov = h.covariance(x, hold=hold, cross=cross, sigma2=sigma2)
   n = h.n_params
   diag = np.diag(H)
   free = np.flatnonzero(~hold & (diag > 0))
   dof = m - free.size
-  sigma2 = cost2 / dof
+  sigma2 = cost2 / dof if sigma2 is None else sigma2
   assert cov.dof == dof
   assert abs(cov.sigma2 - sigma2) <= 1e-12 * sigma2
   var = np.zeros(n)
@@ -68,18 +72,20 @@ def _compare(h, x, hold, H, m, cost2, tol, frames=None, cross=True):
   R = _reference_columns(H, free, cov.sigma2, cols)
   var[cols] = R[cols, np.arange(cols.size)]
   ns = sh.size
-  _check_block(cov.shared, R[sh][:, :ns], var[sh], var[sh], tol)
+  _check_block(cov.shared, R[sh][:, :ns], var[sh], var[sh], tol, ratios)
   DF = fi.shape[1]
   for q, f in enumerate(sel):
     c0 = ns + q * DF
-    _check_block(cov.frames[f], R[fi[f]][:, c0:c0 + DF], var[fi[f]], var[fi[f]], tol)
+    _check_block(cov.frames[f], R[fi[f]][:, c0:c0 + DF], var[fi[f]], var[fi[f]], tol, ratios)
     if cross:
-      _check_block(cov.frame_shared[f], R[fi[f]][:, :ns], var[fi[f]], var[sh], tol)
+      _check_block(cov.frame_shared[f], R[fi[f]][:, :ns], var[fi[f]], var[sh], tol, ratios)
   # std: held exactly 0, unobserved NaN, free sqrt of the diagonal
   assert np.all(cov.std[hold] == 0.0)
   unobs = ~hold & (diag <= 0)
   assert np.all(np.isnan(cov.std[unobs]))
   chk = np.intersect1d(free, cols)
+  if ratios is not None and chk.size:
+    ratios.append(float((np.abs(cov.std[chk] - np.sqrt(var[chk])) / np.sqrt(var[chk])).max()) / tol)
   assert np.allclose(cov.std[chk], np.sqrt(var[chk]), rtol=tol, atol=0)
   return cov
 

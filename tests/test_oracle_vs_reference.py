@@ -10,8 +10,10 @@ pytestmark = pytest.mark.needs_reference
 
 def _planted_names():
   import planted_rigs as pr
+  import reduced_rigs as rr
   return ({"edges-" + pr.shape_id(s): (pr.planted_rig, s) for s in pr.SHAPES} |
-          {"bigboard-" + pr.shape_id(s): (pr.planted_bigboard, s) for s in pr.BIG_SHAPES})
+          {"bigboard-" + pr.shape_id(s): (pr.planted_bigboard, s) for s in pr.BIG_SHAPES} |
+          {"reduced-" + name: (lambda name: (rr.reduced_rig(name),), (name,)) for name in rr.NAMES})
 
 
 PLANTED = _planted_names()
@@ -20,7 +22,8 @@ PLANTED = _planted_names()
 @pytest.mark.parametrize("name", ["tiny", "tiny_rolling", "tiny_fisheye", "tiny_handeye", "tiny_tilted"] + list(PLANTED))
 def test_restatement_is_bit_identical_to_reference(name):
   """... and on the planted rigs of tests/planted_rigs.py: all 42 camera x motion x intrinsics shapes with their views cut to the
-  chunk-edge counts, and the three rigs with an 816-point board."""
+  chunk-edge counts, and the three rigs with an 816-point board; and on the rigs of tests/reduced_rigs.py, chosen by the shape of
+  their reduced system."""
   from oracle import build_reference
   if name in PLANTED:
     make, shape = PLANTED[name]
