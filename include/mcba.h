@@ -630,6 +630,59 @@ int32_t mcba_projection_uncertainty(const mcba_camera_set* cams, const double* c
  * launch), [2] downloads, [3] the whole call; *n_queries (or NULL) = queries launched                                        */
 int32_t mcba_debug_projection_uncertainty_ms(double* ms /*[4]*/, int64_t* n_queries);
 
+/* --- comparing two calibrations: projection difference maps --------------------------------------------------------- */
+/* Where calibration 1 projects what calibration 0 sees at a pixel (csrc/mcba_projdiff.h).  The two camera sets
+ * have the same camera count; the families may differ.  A job is one camera, one reference, one inverse distance and one fit
+ * mode; its queries are a grid generated on the device or a list of pixels, as in mcba_uncertainty_job.
+ *   reference < 0   intrinsics difference: Y = n_b^0(q), q' = project_b^1(R(omega) Y + inv_distance tau), diff = q' - q.
+ *                   (omega, tau) is the job's implied transform, fitted on the device before the map: it minimises sum |diff|^2
+ *                   over the job's FIT PIXELS (a grid fit_grid_w x fit_grid_h or a list fit_uv of their own, at most
+ *                   MCBA_PDIFF_MAX_FIT), of which those inside the focus disc take part (focus_radius <= 0: all) whose inverse
+ *                   under calibration 0 converges and whose projection under calibration 1 is valid at the identity.
+ *                   fit: NONE (identity), ROTATION (3 unknowns), RIGID (6; refused at inv_distance = 0).
+ *   reference = a   transfer difference: Y_a^k = n_a^k(q), Y_b^k = R_ba^k Y_a^k + inv_distance t_ba^k, q_b^k = project_b^k(Y_b^k),
+ *                   diff = q_b^1 - q_b^0 and landing = q_b^0.  No fit (fit and the fit pixels are ignored).  a == camera: exactly 0.
+ * n_c^k(q): the unit ray of the pixel through the exact inverse of camera c under calibration k; poses [C,4,4] rig -> camera.
+ * Handle-less like mcba_projection_uncertainty; same error convention, the caller owns every array.                          */
+#define MCBA_PDIFF_MAX_FIT 65536
+#define MCBA_PDIFF_OK 0
+#define MCBA_PDIFF_NOT_CONVERGED 1     /* the pixel (or where it lands) lies outside the monotone range of a model: NaN        */
+#define MCBA_PDIFF_BEHIND 2            /* the point lies at or behind the plane of the camera, under either calibration: NaN  */
+#define MCBA_PDIFF_NO_FIT 3            /* the job's fit did not end MCBA_PDIFF_FIT_OK: NaN                                      */
+#define MCBA_PDIFF_FIT_OK 0
+#define MCBA_PDIFF_FIT_TOO_FEW 1       /* fewer than 2 (ROTATION) or 3 (RIGID) fit pixels take part                            */
+#define MCBA_PDIFF_FIT_NOT_CONVERGED 2
+#define MCBA_PDIFF_FIT_DEGENERATE 3    /* the damped system is not well posed                                                  */
+#define MCBA_PDIFF_MODE_NONE 0
+#define MCBA_PDIFF_MODE_ROTATION 1
+#define MCBA_PDIFF_MODE_RIGID 2
+typedef struct mcba_projdiff_job {
+  int32_t camera, reference;     /* b; a or < 0 = the camera itself */
+  double inv_distance;           /* >= 0, finite */
+  int32_t fit;                   /* MCBA_PDIFF_MODE_* */
+  int32_t fit_grid_w, fit_grid_h;  /* fit_grid_w > 0: the fit pixels are a grid (fit_u0 + ix fit_du, fit_v0 + iy fit_dv) */
+  double fit_u0, fit_v0, fit_du, fit_dv;
+  int64_t fit_n;                 /* fit_grid_w == 0: fit_n fit pixels */
+  const double* fit_uv;          /* [fit_n,2] */
+  double focus_u, focus_v, focus_radius;   /* pixels; focus_radius <= 0: the whole image */
+  int32_t grid_w, grid_h;        /* the queries, as in mcba_uncertainty_job */
+  double u0, v0, du, dv;
+  int64_t n;
+  const double* uv;              /* [n,2] pixels */
+} mcba_projdiff_job;
+/* Outputs.  Per job: transform [n_jobs,6] rotation vector | translation (0 for a job without a fit, NaN for a fit that did not
+ * end OK); fit_info [n_jobs,5] = n_fit, iterations (linearisations), RMS of |diff| over the fit pixels before and after the fit,
+ * MCBA_PDIFF_FIT_* (each an exact double; NaN RMS where there is none).  Either may be NULL.  Per query, the jobs' queries one after
+ * the other (n_total): diff [n_total,2]; magnitude [n_total] or NULL; landing [n_total,2] or NULL (NaN for intrinsics jobs); status
+ * [n_total] MCBA_PDIFF_*.  Everything of a query is NaN unless its status is OK.  Zero queries launch nothing, the fit
+ * included: transform and fit_info are then those of jobs without a fit (0, n_fit 0, NaN RMS, MCBA_PDIFF_FIT_OK).            */
+int32_t mcba_projection_diff(const mcba_camera_set* cams0, const double* poses0, const mcba_camera_set* cams1, const double* poses1,
+                             int32_t n_jobs, const mcba_projdiff_job* jobs, double* transform, double* fit_info, double* diff,
+                             double* magnitude, double* landing, uint8_t* status);
+/* timing of the last mcba_projection_diff call of this thread, milliseconds: [0] uploads, [1] fit kernel, [2] map kernel (both by
+ * HIP events), [3] downloads, [4] the whole call; *n_queries (or NULL) = queries launched                                       */
+int32_t mcba_debug_projection_diff_ms(double* ms /*[5]*/, int64_t* n_queries);
+
 /* --- solve -------------------------------------------------------------------------------------------------- */
 /* Trust-region least squares: replaces scipy.optimize.least_squares(method='trf', x_scale='jac', jac_sparsity=S,
  * loss, f_scale, ftol, max_nfev) at calibration.py:209-210.  x is updated in place to `res.x`.                 */

@@ -103,12 +103,24 @@ class UncertaintyJob(C.Structure):   # mcba_uncertainty_job
               ("v0", C.c_double), ("du", C.c_double), ("dv", C.c_double), ("n", C.c_int64), ("uv", c_double_p)]
 
 
+class ProjDiffJob(C.Structure):   # mcba_projdiff_job
+  _fields_ = [("camera", C.c_int32), ("reference", C.c_int32), ("inv_distance", C.c_double), ("fit", C.c_int32),
+              ("fit_grid_w", C.c_int32), ("fit_grid_h", C.c_int32), ("fit_u0", C.c_double), ("fit_v0", C.c_double),
+              ("fit_du", C.c_double), ("fit_dv", C.c_double), ("fit_n", C.c_int64), ("fit_uv", c_double_p), ("focus_u", C.c_double),
+              ("focus_v", C.c_double), ("focus_radius", C.c_double), ("grid_w", C.c_int32), ("grid_h", C.c_int32), ("u0", C.c_double),
+              ("v0", C.c_double), ("du", C.c_double), ("dv", C.c_double), ("n", C.c_int64), ("uv", c_double_p)]
+
+
 TRI_OK, TRI_TOO_FEW, TRI_DEGENERATE, TRI_NOT_CONVERGED, TRI_BEHIND = 0, 1, 2, 3, 4   # MCBA_TRI_*
 TRI_MAX_CAMERAS = 64                                  # MCBA_TRI_MAX_CAMERAS
 RIG_OK, RIG_TOO_FEW, RIG_DEGENERATE, RIG_NOT_CONVERGED, RIG_BEHIND = 0, 1, 2, 3, 4   # MCBA_RIG_*
 RIG_MAX_CAMERAS = 64                                  # MCBA_RIG_MAX_CAMERAS
 UNC_OK, UNC_NOT_CONVERGED, UNC_BEHIND, UNC_UNCONSTRAINED = 0, 1, 2, 3   # MCBA_UNC_*
 UNC_MAX_K = 48                                        # MCBA_UNC_MAX_K
+PDIFF_OK, PDIFF_NOT_CONVERGED, PDIFF_BEHIND, PDIFF_NO_FIT = 0, 1, 2, 3   # MCBA_PDIFF_*
+PDIFF_FIT_OK, PDIFF_FIT_TOO_FEW, PDIFF_FIT_NOT_CONVERGED, PDIFF_FIT_DEGENERATE = 0, 1, 2, 3   # MCBA_PDIFF_FIT_*
+PDIFF_MODE_NONE, PDIFF_MODE_ROTATION, PDIFF_MODE_RIGID = 0, 1, 2   # MCBA_PDIFF_MODE_*
+PDIFF_MAX_FIT = 65536                                 # MCBA_PDIFF_MAX_FIT
 PIXEL_U8, PIXEL_F32 = 0, 1                            # MCBA_PIXEL_*
 UNDISTORT_OK, UNDISTORT_NOT_CONVERGED = 0, 1          # MCBA_UNDISTORT_*
 
@@ -167,6 +179,9 @@ SYMBOLS = [
   ("mcba_projection_uncertainty", C.c_int32, [C.POINTER(CameraSet), c_double_p, C.c_int32, C.POINTER(UncertaintyJob), c_double_p,
                                               c_double_p, c_uint8_p]),
   ("mcba_debug_projection_uncertainty_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_projection_diff", C.c_int32, [C.POINTER(CameraSet), c_double_p, C.POINTER(CameraSet), c_double_p, C.c_int32,
+                                       C.POINTER(ProjDiffJob), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_uint8_p]),
+  ("mcba_debug_projection_diff_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_error_stats", C.c_int32, [H, c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), c_double_p,
                                    C.POINTER(C.c_int64), c_double_p]),
   ("mcba_error_count", C.c_int32, [H, C.c_int32, C.POINTER(C.c_int64)]),

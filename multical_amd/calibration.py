@@ -812,6 +812,78 @@ class Calibration(parameters.Parameters):
            f"below sigma={sigma:.3f} px")
     return u
 
+  # --- comparing two calibrations -----------------------------------------------------------------
+  def _other_rig(self, other):
+    """(cameras, camera_poses [C, 4, 4]) of `other` in this calibration's camera order: a Calibration (same order), or what
+    import_calib.load_calibration returns (matched by name)"""
+    if isinstance(other, Calibration):
+      if other.size.cameras != self.size.cameras:
+        raise ValueError(f"projection_diff: {self.size.cameras} and {other.size.cameras} cameras")
+      return list(other.cameras), np.asarray(other.camera_poses.poses)
+    names, theirs = list(self.camera_poses.names), list(other.names)
+    missing = [n for n in names if n not in theirs]
+    if missing:
+      raise ValueError(f"projection_diff: the other calibration has no camera {missing} (it has {theirs})")
+    pick = [theirs.index(n) for n in names]
+    return [other.cameras[i] for i in pick], np.asarray(other.camera_poses, dtype=np.float64)[pick]
+
+  def projection_diff(self, other, cameras=None, reference=None, distance=np.inf, grid=(16, 12), pixels=None, fit="auto",
+                      fit_grid=(60, 40), focus=None, sigmas=False):
+    """Where `other` (calibration 1: a Calibration, or what import_calib.load_calibration returns, matched by camera name) projects
+    what this calibration (0) sees at a pixel, as a map over the image of each of `cameras` (multical_amd.compare, one device call).
+    reference=None: the intrinsics difference behind the implied transform fitted over `fit_grid` inside `focus` = (u, v, radius)
+    (fit: "auto" = "rotation" at infinity, "rigid" at a finite distance; "none"); reference=a: the transfer difference against
+    camera a -- has the camera moved against a? -- with `landing`, where the point is seen under this calibration.  Returns
+    struct(diff, magnitude, landing, pixels, status, transform, fit) as compare.projection_diff does.
+    sigmas=True (transfer mode only): adds d = sqrt(diff^T (C0 + C1)^-1 diff), C^k each calibration's own
+    projection_uncertainty(reference=a) at the same pixels; both sides must be Calibrations with observations (ValueError
+    otherwise).  d is calibrated -- chi-distributed with two degrees of freedom under agreement -- ONLY when the two calibrations
+    come from independent data sets: two fits of the same detections share their noise, and d then overstates the agreement."""
+    from . import compare
+    cams1, poses1 = self._other_rig(other)
+    out = compare.projection_diff(list(self.cameras), np.asarray(self.camera_poses.poses), cams1, poses1, query_cameras=cameras,
+                                  reference=reference, distance=distance, grid=grid, pixels=pixels, fit=fit, fit_grid=fit_grid,
+                                  focus=focus)
+    if not sigmas:
+      return out
+    if reference is None:
+      raise ValueError("projection_diff: sigmas=True needs a reference camera (the fit of the intrinsics mode absorbs part of the "
+                       "difference, so C0 + C1 is not its covariance)")
+    if not isinstance(other, Calibration) or not np.asarray(other.point_table.valid).any() or not np.asarray(self.point_table.valid).any():
+      raise ValueError("projection_diff: sigmas=True needs two Calibrations with observations (each side's covariance comes from "
+                       "its own data)")
+    u0, u1 = (c.projection_uncertainty(cameras=cameras, reference=reference, distance=distance, grid=grid, pixels=pixels)
+              for c in (self, other))
+    return out._extend(d=compare.significance(out.diff, u0.cov, u1.cov), cov0=u0.cov, cov1=u1.cov)
+
+  def report_projection_diff(self, other, stage="", reference=None, distance=np.inf):
+    """One line per camera through the "calibration" logger: median and maximum |diff| (px) over the default 16 x 12 grid, the value
+    at the image centre, the implied rotation in mrad (and the translation in mm -- board units x 1000 -- at a finite distance) and
+    the RMS over the fit pixels before -> after the fit; in transfer mode the fit figures are left out."""
+    from . import compare
+    r = self.projection_diff(other, reference=reference, distance=distance)
+    names = getattr(self.camera_poses, "names", None) or [f"cam{i}" for i in range(self.size.cameras)]
+    for c in range(self.size.cameras):
+      mag = r.magnitude[c]
+      ok = r.status[c] == compare.OK
+      if not ok.any():
+        why = "the fit of the implied transform failed" if (r.status[c] == compare.NO_FIT).all() else "no grid cell is OK"
+        info(f"{stage} {names[c]}: projection difference not defined ({why})")
+        continue
+      w, h = self.cameras[c].image_size
+      mid = self.projection_diff(other, cameras=[c], reference=reference, distance=distance, pixels=[[0.5 * (w - 1), 0.5 * (h - 1)]],
+                                 fit_grid=(60, 40)).magnitude[0]
+      line = (f"{stage} {names[c]}: projection difference median={float(np.median(mag[ok])):.4f} max={float(mag[ok].max()):.4f} "
+              f"centre={float(mid):.4f} px")
+      if reference is None:
+        t = r.transform[c]
+        line += f", implied rotation={1e3 * float(np.linalg.norm(t[:3])):.4f} mrad"
+        if not np.isinf(distance):
+          line += f", translation={1e3 * float(np.linalg.norm(t[3:])):.4f} mm"
+        line += f", fit RMS {float(r.fit.rms_before[c]):.4f} -> {float(r.fit.rms_after[c]):.4f} px over {int(r.fit.n_fit[c])} pixels"
+      info(line)
+    return r
+
 
 def split_std(calib, std):
   """A vector over calib.param_vec (standard deviations) split into the enabled blocks: camera_poses [C, 6], board_poses
