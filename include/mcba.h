@@ -683,6 +683,80 @@ int32_t mcba_projection_diff(const mcba_camera_set* cams0, const double* poses0,
  * HIP events), [3] downloads, [4] the whole call; *n_queries (or NULL) = queries launched                                       */
 int32_t mcba_debug_projection_diff_ms(double* ms /*[5]*/, int64_t* n_queries);
 
+/* --- planning the next captures: information gain of candidate views -------------------------------------------------- */
+/* What a new view of a board adds to the intrinsics of the camera that sees it, and what it does to the projection uncertainty
+ * over a focus region (csrc/mcba_guidance.h).  Per camera c: W [KI_c, r] row-major with W W^T = the covariance of
+ * its columns fx fy cx cy dist.. (KI_c = 4 + the camera's own coefficient count; the W of a rig-frame job of
+ * mcba_projection_uncertainty, camera rows only), r = 0 .. MCBA_GUIDE_MAX_R (0: everything held), `unconstrained` != 0: an
+ * intrinsic that no residual constrains and that is not held, and the image size.
+ * A view is a set of points seen by `camera` with n_nuisance = 0, 3 or 6 free parameters of its own (nothing | a rotation | a
+ * rigid motion), eliminated before anything is reported:
+ *   board >= 0   the points of that board (board_points [n_boards, board_stride, 3], the first board_n[board] of a board) at
+ *                the board-in-camera pose `pose` (3 x 4, row-major); a point is visible in front of the camera, inside the image
+ *                by `margin` pixels, where the model is monotone;
+ *   board < 0    a focus: the unit rays of a grid or a list of pixels (as in mcba_uncertainty_job) at inv_distance (0: directions;
+ *                n_nuisance = 6 needs inv_distance > 0); a pixel is visible where the exact inverse converges.
+ * S_v [r, r] is the Schur complement of the nuisance block in the Gram matrix of the rows [Kc W | E] of the visible points.
+ * A_v = S_v / sigma2; against a base B_c (I at first, + A of every pick):  gain = (log det(B_c + A_v) - log det B_c) / 2 in nats,
+ * focus_rms = sqrt(trace((B_c + A_v)^-1 Q_c) / n) in pixels, Q_c and n the S and the visible count of foci[c].
+ * Greedy selection: n_picks rounds; a round scores every candidate, takes per camera the best by `criterion` (ties: the lowest
+ * index; a view is picked once), adds its A to B_c.  Handle-less like mcba_projection_uncertainty; same error convention, the
+ * caller owns every array.                                                                                                     */
+#define MCBA_GUIDE_MAX_R 18
+#define MCBA_GUIDE_OK 0
+#define MCBA_GUIDE_TOO_FEW 1        /* fewer than min_points points are visible                                               */
+#define MCBA_GUIDE_DEGENERATE 2     /* the nuisance block is not positive definite (collinear points, ...)                    */
+#define MCBA_GUIDE_UNCONSTRAINED 3  /* the camera has an unconstrained intrinsic: no finite prior                             */
+#define MCBA_GUIDE_BY_FOCUS 0
+#define MCBA_GUIDE_BY_GAIN 1
+typedef struct mcba_guidance_camera {
+  int32_t r, unconstrained;
+  const double* W;               /* [KI_c, r] */
+  double image_w, image_h;
+} mcba_guidance_camera;
+typedef struct mcba_guidance_view {
+  int32_t camera, n_nuisance, min_points, board;
+  double pose[12];               /* board >= 0 */
+  double inv_distance;           /* board < 0: >= 0, finite */
+  int32_t grid_w, grid_h;        /* board < 0, grid_w > 0: a grid, as in mcba_uncertainty_job */
+  double u0, v0, du, dv;
+  int64_t n;                     /* board < 0, grid_w == 0: n pixels */
+  const double* uv;              /* [n,2] */
+} mcba_guidance_view;
+/* Outputs; rs = max(1, the largest r of the call) is the row stride of every matrix, camera c uses the leading r_c x r_c block.
+ * Per view: n_visible, status MCBA_GUIDE_*, gain and focus_rms against B = I (NaN unless OK; a camera with r = 0: OK, 0, 0, and
+ * n_visible 0: nothing is launched for it), S [n_views, rs, rs] or NULL (0 unless OK).  Per camera: focus_status, focus_n_visible,
+ * focus_before (focus_rms of the base I; NaN without an OK focus), Q [C, rs, rs] (each or NULL); picks [C, n_picks] (view index, -1:
+ * none left), pick_gain (conditional on the earlier picks), pick_focus_rms (after the pick); posterior [C, rs, rs] or NULL =
+ * (B_c)^-1 after the last pick.  round_gain / round_focus_rms [n_picks, n_views] or NULL: the scores of every round.           */
+typedef struct mcba_guidance_result {
+  int32_t* n_visible;
+  uint8_t* status;
+  double* gain;
+  double* focus_rms;
+  double* S;
+  uint8_t* focus_status;
+  int32_t* focus_n_visible;
+  double* focus_before;
+  double* Q;
+  int32_t* picks;
+  double* pick_gain;
+  double* pick_focus_rms;
+  double* posterior;
+  double* round_gain;
+  double* round_focus_rms;
+} mcba_guidance_result;
+/* info [C]; views [n_views]: board views, or views of pixels (board < 0) scored like them; foci [C] or NULL (an entry with
+ * camera < 0: no focus for that camera; otherwise camera == its index, board < 0).
+ * Zero views launch nothing (picks -1, NaN).                                                                                  */
+int32_t mcba_view_information(const mcba_camera_set* cams, const mcba_guidance_camera* info, int32_t n_boards, int32_t board_stride,
+                              const int32_t* board_n, const double* board_points, double margin, double sigma2, int32_t n_views,
+                              const mcba_guidance_view* views, const mcba_guidance_view* foci, int32_t n_picks, int32_t criterion,
+                              const mcba_guidance_result* out);
+/* timing of the last mcba_view_information call of this thread, milliseconds: [0] uploads, [1] k_view_schur and the scoring
+ * rounds with their transfers (HIP events), [2] downloads, [3] the whole call; *n_views (or NULL) = views launched (foci too)  */
+int32_t mcba_debug_view_information_ms(double* ms /*[4]*/, int64_t* n_views);
+
 /* --- solve -------------------------------------------------------------------------------------------------- */
 /* Trust-region least squares: replaces scipy.optimize.least_squares(method='trf', x_scale='jac', jac_sparsity=S,
  * loss, f_scale, ftol, max_nfev) at calibration.py:209-210.  x is updated in place to `res.x`.                 */

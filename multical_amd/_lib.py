@@ -111,6 +111,23 @@ class ProjDiffJob(C.Structure):   # mcba_projdiff_job
               ("v0", C.c_double), ("du", C.c_double), ("dv", C.c_double), ("n", C.c_int64), ("uv", c_double_p)]
 
 
+class GuidanceCamera(C.Structure):   # mcba_guidance_camera
+  _fields_ = [("r", C.c_int32), ("unconstrained", C.c_int32), ("W", c_double_p), ("image_w", C.c_double), ("image_h", C.c_double)]
+
+
+class GuidanceView(C.Structure):   # mcba_guidance_view
+  _fields_ = [("camera", C.c_int32), ("n_nuisance", C.c_int32), ("min_points", C.c_int32), ("board", C.c_int32),
+              ("pose", C.c_double * 12), ("inv_distance", C.c_double), ("grid_w", C.c_int32), ("grid_h", C.c_int32), ("u0", C.c_double),
+              ("v0", C.c_double), ("du", C.c_double), ("dv", C.c_double), ("n", C.c_int64), ("uv", c_double_p)]
+
+
+class GuidanceResult(C.Structure):   # mcba_guidance_result
+  _fields_ = [("n_visible", C.POINTER(C.c_int32)), ("status", c_uint8_p), ("gain", c_double_p), ("focus_rms", c_double_p),
+              ("S", c_double_p), ("focus_status", c_uint8_p), ("focus_n_visible", C.POINTER(C.c_int32)), ("focus_before", c_double_p),
+              ("Q", c_double_p), ("picks", C.POINTER(C.c_int32)), ("pick_gain", c_double_p), ("pick_focus_rms", c_double_p),
+              ("posterior", c_double_p), ("round_gain", c_double_p), ("round_focus_rms", c_double_p)]
+
+
 TRI_OK, TRI_TOO_FEW, TRI_DEGENERATE, TRI_NOT_CONVERGED, TRI_BEHIND = 0, 1, 2, 3, 4   # MCBA_TRI_*
 TRI_MAX_CAMERAS = 64                                  # MCBA_TRI_MAX_CAMERAS
 RIG_OK, RIG_TOO_FEW, RIG_DEGENERATE, RIG_NOT_CONVERGED, RIG_BEHIND = 0, 1, 2, 3, 4   # MCBA_RIG_*
@@ -121,6 +138,9 @@ PDIFF_OK, PDIFF_NOT_CONVERGED, PDIFF_BEHIND, PDIFF_NO_FIT = 0, 1, 2, 3   # MCBA_
 PDIFF_FIT_OK, PDIFF_FIT_TOO_FEW, PDIFF_FIT_NOT_CONVERGED, PDIFF_FIT_DEGENERATE = 0, 1, 2, 3   # MCBA_PDIFF_FIT_*
 PDIFF_MODE_NONE, PDIFF_MODE_ROTATION, PDIFF_MODE_RIGID = 0, 1, 2   # MCBA_PDIFF_MODE_*
 PDIFF_MAX_FIT = 65536                                 # MCBA_PDIFF_MAX_FIT
+GUIDE_OK, GUIDE_TOO_FEW, GUIDE_DEGENERATE, GUIDE_UNCONSTRAINED = 0, 1, 2, 3   # MCBA_GUIDE_*
+GUIDE_BY_FOCUS, GUIDE_BY_GAIN = 0, 1                  # MCBA_GUIDE_BY_*
+GUIDE_MAX_R = 18                                      # MCBA_GUIDE_MAX_R
 PIXEL_U8, PIXEL_F32 = 0, 1                            # MCBA_PIXEL_*
 UNDISTORT_OK, UNDISTORT_NOT_CONVERGED = 0, 1          # MCBA_UNDISTORT_*
 
@@ -182,6 +202,10 @@ SYMBOLS = [
   ("mcba_projection_diff", C.c_int32, [C.POINTER(CameraSet), c_double_p, C.POINTER(CameraSet), c_double_p, C.c_int32,
                                        C.POINTER(ProjDiffJob), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_uint8_p]),
   ("mcba_debug_projection_diff_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_view_information", C.c_int32, [C.POINTER(CameraSet), C.POINTER(GuidanceCamera), C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                        c_double_p, C.c_double, C.c_double, C.c_int32, C.POINTER(GuidanceView), C.POINTER(GuidanceView),
+                                        C.c_int32, C.c_int32, C.POINTER(GuidanceResult)]),
+  ("mcba_debug_view_information_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_error_stats", C.c_int32, [H, c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), c_double_p,
                                    C.POINTER(C.c_int64), c_double_p]),
   ("mcba_error_count", C.c_int32, [H, C.c_int32, C.POINTER(C.c_int64)]),

@@ -884,6 +884,59 @@ class Calibration(parameters.Parameters):
       info(line)
     return r
 
+  # --- planning the next captures -----------------------------------------------------------------
+  def suggest_views(self, n=3, cameras=None, board=0, candidates=None, focus_grid=(16, 12), focus_distance=np.inf, criterion="focus",
+                    hold=None, sigma2=None):
+    """Where to hold board `board` next: per camera of `cameras` (indices; None: all) the n candidate views that, one after the
+    other, reduce the RMS projection uncertainty over the focus grid most (criterion="focus"; after the implied rotation -- or, at
+    a finite focus_distance, rigid motion -- is fitted out) or carry the most information on its intrinsics (criterion="gain"),
+    under `covariance(hold, sigma2)` (multical_amd.guidance, one covariance and one device call).  A candidate is a static capture
+    in a new frame with a free rig pose, seen by that camera alone; candidates: None (guidance.candidate_poses) or {camera: poses
+    [m, 4, 4] board in camera}.  Returns struct(cameras, poses [C', n, 4, 4], candidate_index, gain [C', n] (nats, each conditional
+    on the earlier picks), focus_rms_before [C'], focus_rms_after [C', n] (px), n_visible, status (guidance.OK / TOO_FEW /
+    UNCONSTRAINED), candidates, scores, sigma2, dof)."""
+    from . import guidance
+    if self.optimize["boards"] is True:
+      raise ValueError("suggest_views: not supported with the boards block optimised (the board points would join the shared "
+                       "system, as for projection_uncertainty)")
+    cov = self.covariance(hold=hold, sigma2=sigma2)
+    camera_index, _ = self._shared_layout()
+    out = guidance.suggest_views(list(self.cameras), cov, camera_index, list(self.boards), n=n, query_cameras=cameras, board=board,
+                                 candidates=candidates, focus_grid=focus_grid, focus_distance=focus_distance, criterion=criterion)
+    return out._extend(sigma2=cov.sigma2, dof=cov.dof)
+
+  def report_view_suggestions(self, stage="", n=3, board=0, criterion="focus"):
+    """One line per camera and pick through the "calibration" logger: the distance of the board's centre, the image region it
+    lands in (a 3 x 3 naming of where its centre projects), its tilt against the optical axis, the information gain and the focus
+    RMS before -> after the pick in px."""
+    from . import guidance
+    s = self.suggest_views(n=n, board=board, criterion=criterion)
+    names = getattr(self.camera_poses, "names", None) or [f"cam{i}" for i in range(self.size.cameras)]
+    pts = np.asarray(self.boards[board].adjusted_points, dtype=np.float64).reshape(-1, 3)
+    centre = 0.5 * (pts.min(axis=0) + pts.max(axis=0))
+    for i, c in enumerate(s.cameras):
+      if s.status[i] != guidance.OK:
+        why = "an intrinsic is unconstrained" if s.status[i] == guidance.UNCONSTRAINED else "no candidate is usable"
+        info(f"{stage} {names[c]}: no view suggested ({why})")
+        continue
+      before = float(s.focus_rms_before[i])
+      for k in range(n):
+        if s.candidate_index[i, k] < 0:
+          break
+        T = s.poses[i, k]
+        X = T[:3, :3] @ centre + T[:3, 3]
+        w, h = self.cameras[c].image_size
+        K = np.asarray(self.cameras[c].intrinsic, dtype=np.float64)
+        u, v = K[0, 0] * X[0] / X[2] + K[0, 2], K[1, 1] * X[1] / X[2] + K[1, 2]
+        col = ("left", "centre", "right")[int(np.clip(3.0 * u / w, 0, 2))]
+        row = ("top", "middle", "bottom")[int(np.clip(3.0 * v / h, 0, 2))]
+        tilt = float(np.degrees(np.arccos(np.clip(abs(T[2, 2]), 0.0, 1.0))))
+        after = float(s.focus_rms_after[i, k])
+        info(f"{stage} {names[c]} view {k + 1}: board at distance={float(np.linalg.norm(X)):.3f}, {row} {col}, tilt={tilt:.0f} deg, "
+             f"{int(s.n_visible[i, k])} corners, gain={float(s.gain[i, k]):.3f} nats, focus RMS {before:.4f} -> {after:.4f} px")
+        before = after
+    return s
+
 
 def split_std(calib, std):
   """A vector over calib.param_vec (standard deviations) split into the enabled blocks: camera_poses [C, 6], board_poses
