@@ -757,6 +757,74 @@ int32_t mcba_view_information(const mcba_camera_set* cams, const mcba_guidance_c
  * rounds with their transfers (HIP events), [2] downloads, [3] the whole call; *n_views (or NULL) = views launched (foci too)  */
 int32_t mcba_debug_view_information_ms(double* ms /*[4]*/, int64_t* n_views);
 
+/* --- planning the next captures: views seen by several cameras ------------------------------------------------------- */
+/* What a new view of a board that several cameras of a group see at once adds to their intrinsics AND their poses, and what it
+ * does to the transfer uncertainty between them (csrc/mcba_rigview.h).  `cams` is the group; camera_poses
+ * [C, 3, 4] rig -> camera.  The prior is Sigma = F F^T over the stored parameters of the group, F of rank r; per camera c
+ * W [MCBA_RIG_COLUMNS, r] row-major = the rows of F in the device columns of c: fx fy cx cy k0..k13 (18, rows of coefficients the
+ * camera lacks are 0) | the left perturbation (omega, tau) of camera_poses[c] (6) -- blockdiag(camera map, pose map) F[rows of c];
+ * `unconstrained` != 0: a parameter of c that no residual constrains and that is not held.
+ * A view is board `board` at the board-in-rig pose `pose` (3 x 4, row-major) in a new frame whose rig pose is free; camera c sees
+ * the points that pass the visibility test of mcba_view_information and CONTRIBUTES with at least min_points (and one) of them.
+ * A [r, r] = sigma2 A_v is the Schur complement of the frame pose in the Gram matrix of the contributing cameras' rows; against a
+ * base B (I at first, + A_v of every pick): gain = (log det(B + A_v) - log det B) / 2 in nats.  The focus: the pixels of a grid of
+ * camera `reference` at inv_distance, transferred into every member camera b (mcba_projection_uncertainty with reference = a);
+ * Q = sum_b sum_pixels (J W_ab)^T (J W_ab) over the n_ok queries that are MCBA_UNC_OK, focus_rms = sqrt(trace((B + A_v)^-1 Q) / n_ok).
+ * Greedy selection of n_picks views for the rig by `criterion` (MCBA_GUIDE_BY_*; ties: the lowest index; a view is picked once).
+ * Refused, with nothing launched: r > MCBA_RIG_MAX_R (use a smaller camera group), n_views r^2 8 bytes above workspace_mb (pass
+ * fewer candidates per call), boards != 0 (the board points are parameters of the calibration).  r = 0 or n_views = 0: nothing is
+ * launched, every gain is 0.  Handle-less like mcba_view_information; same error convention, the caller owns every array.       */
+#define MCBA_RIG_MAX_R 128
+#define MCBA_RIG_COLUMNS 24
+typedef struct mcba_rig_camera {
+  int32_t unconstrained, reserved;
+  const double* W;               /* [MCBA_RIG_COLUMNS, r] */
+  double image_w, image_h;
+} mcba_rig_camera;
+typedef struct mcba_rig_view {
+  int32_t board, min_points;
+  double pose[12];
+} mcba_rig_view;
+typedef struct mcba_rig_focus {
+  int32_t reference, n_members;
+  const int32_t* members;        /* [n_members] the cameras b (the reference itself is skipped) */
+  int32_t grid_w, grid_h;        /* pixel (ix, iy) = (u0 + ix du, v0 + iy dv) of the reference camera */
+  double u0, v0, du, dv;
+  double inv_distance;           /* >= 0, finite */
+} mcba_rig_focus;
+/* Outputs; rs = max(1, r) is the row stride of every matrix.  Per view: n_cameras (contributing), n_visible [n_views, C], status
+ * MCBA_GUIDE_* (TOO_FEW: fewer than min_cameras contribute; UNCONSTRAINED: a contributing camera is; DEGENERATE: the frame pose is
+ * not determined), gain and focus_rms against B = I (NaN unless OK), A [n_views, rs, rs] or NULL (0 unless OK).  The focus:
+ * focus_status, focus_n (n_ok), focus_before, Q [rs, rs] (each or NULL).  picks [n_picks] (view, -1: none left), pick_gain
+ * (conditional on the earlier picks), pick_focus_rms (after the pick); posterior [rs, rs] or NULL = B^-1 after the last pick;
+ * round_gain / round_focus_rms [n_picks, n_views] or NULL.                                                                     */
+typedef struct mcba_rig_result {
+  int32_t* n_cameras;
+  int32_t* n_visible;
+  uint8_t* status;
+  double* gain;
+  double* focus_rms;
+  double* A;
+  uint8_t* focus_status;
+  int32_t* focus_n;
+  double* focus_before;
+  double* Q;
+  int32_t* picks;
+  double* pick_gain;
+  double* pick_focus_rms;
+  double* posterior;
+  double* round_gain;
+  double* round_focus_rms;
+} mcba_rig_result;
+int32_t mcba_rig_view_information(const mcba_camera_set* cams, const double* camera_poses, int32_t r, const mcba_rig_camera* info,
+                                  int32_t boards, int32_t n_boards, int32_t board_stride, const int32_t* board_n,
+                                  const double* board_points, int32_t n_views, const mcba_rig_view* views, int32_t min_cameras,
+                                  double margin, double sigma2, const mcba_rig_focus* focus, int32_t n_picks, int32_t criterion,
+                                  int32_t workspace_mb, const mcba_rig_result* out);
+/* timing of the last mcba_rig_view_information call of this thread, milliseconds: [0] uploads, [1] the kernels and the scoring
+ * rounds with their transfers (HIP events), [2] downloads, [3] the whole call; *n_slots (or NULL) = (view, camera) slots launched */
+int32_t mcba_debug_rig_view_information_ms(double* ms /*[4]*/, int64_t* n_slots);
+
 /* --- solve -------------------------------------------------------------------------------------------------- */
 /* Trust-region least squares: replaces scipy.optimize.least_squares(method='trf', x_scale='jac', jac_sparsity=S,
  * loss, f_scale, ftol, max_nfev) at calibration.py:209-210.  x is updated in place to `res.x`.                 */

@@ -135,12 +135,34 @@ RIG_MAX_CAMERAS = 64                                  # MCBA_RIG_MAX_CAMERAS
 UNC_OK, UNC_NOT_CONVERGED, UNC_BEHIND, UNC_UNCONSTRAINED = 0, 1, 2, 3   # MCBA_UNC_*
 UNC_MAX_K = 48                                        # MCBA_UNC_MAX_K
 PDIFF_OK, PDIFF_NOT_CONVERGED, PDIFF_BEHIND, PDIFF_NO_FIT = 0, 1, 2, 3   # MCBA_PDIFF_*
+class RigCamera(C.Structure):   # mcba_rig_camera
+  _fields_ = [("unconstrained", C.c_int32), ("reserved", C.c_int32), ("W", c_double_p), ("image_w", C.c_double), ("image_h", C.c_double)]
+
+
+class RigView(C.Structure):   # mcba_rig_view
+  _fields_ = [("board", C.c_int32), ("min_points", C.c_int32), ("pose", C.c_double * 12)]
+
+
+class RigFocus(C.Structure):   # mcba_rig_focus
+  _fields_ = [("reference", C.c_int32), ("n_members", C.c_int32), ("members", C.POINTER(C.c_int32)), ("grid_w", C.c_int32),
+              ("grid_h", C.c_int32), ("u0", C.c_double), ("v0", C.c_double), ("du", C.c_double), ("dv", C.c_double),
+              ("inv_distance", C.c_double)]
+
+
+class RigResult(C.Structure):   # mcba_rig_result
+  _fields_ = [("n_cameras", C.POINTER(C.c_int32)), ("n_visible", C.POINTER(C.c_int32)), ("status", c_uint8_p), ("gain", c_double_p),
+              ("focus_rms", c_double_p), ("A", c_double_p), ("focus_status", c_uint8_p), ("focus_n", C.POINTER(C.c_int32)),
+              ("focus_before", c_double_p), ("Q", c_double_p), ("picks", C.POINTER(C.c_int32)), ("pick_gain", c_double_p),
+              ("pick_focus_rms", c_double_p), ("posterior", c_double_p), ("round_gain", c_double_p), ("round_focus_rms", c_double_p)]
+
+
 PDIFF_FIT_OK, PDIFF_FIT_TOO_FEW, PDIFF_FIT_NOT_CONVERGED, PDIFF_FIT_DEGENERATE = 0, 1, 2, 3   # MCBA_PDIFF_FIT_*
 PDIFF_MODE_NONE, PDIFF_MODE_ROTATION, PDIFF_MODE_RIGID = 0, 1, 2   # MCBA_PDIFF_MODE_*
 PDIFF_MAX_FIT = 65536                                 # MCBA_PDIFF_MAX_FIT
 GUIDE_OK, GUIDE_TOO_FEW, GUIDE_DEGENERATE, GUIDE_UNCONSTRAINED = 0, 1, 2, 3   # MCBA_GUIDE_*
 GUIDE_BY_FOCUS, GUIDE_BY_GAIN = 0, 1                  # MCBA_GUIDE_BY_*
 GUIDE_MAX_R = 18                                      # MCBA_GUIDE_MAX_R
+RIG_MAX_R, RIG_COLUMNS = 128, 24                      # MCBA_RIG_MAX_R, MCBA_RIG_COLUMNS
 PIXEL_U8, PIXEL_F32 = 0, 1                            # MCBA_PIXEL_*
 UNDISTORT_OK, UNDISTORT_NOT_CONVERGED = 0, 1          # MCBA_UNDISTORT_*
 
@@ -206,6 +228,11 @@ SYMBOLS = [
                                         c_double_p, C.c_double, C.c_double, C.c_int32, C.POINTER(GuidanceView), C.POINTER(GuidanceView),
                                         C.c_int32, C.c_int32, C.POINTER(GuidanceResult)]),
   ("mcba_debug_view_information_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_rig_view_information", C.c_int32, [C.POINTER(CameraSet), c_double_p, C.c_int32, C.POINTER(RigCamera), C.c_int32, C.c_int32,
+                                            C.c_int32, C.POINTER(C.c_int32), c_double_p, C.c_int32, C.POINTER(RigView), C.c_int32,
+                                            C.c_double, C.c_double, C.POINTER(RigFocus), C.c_int32, C.c_int32, C.c_int32,
+                                            C.POINTER(RigResult)]),
+  ("mcba_debug_rig_view_information_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_error_stats", C.c_int32, [H, c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), c_double_p,
                                    C.POINTER(C.c_int64), c_double_p]),
   ("mcba_error_count", C.c_int32, [H, C.c_int32, C.POINTER(C.c_int64)]),

@@ -937,6 +937,59 @@ class Calibration(parameters.Parameters):
         before = after
     return s
 
+  # --- views that several cameras see --------------------------------------------------------------
+  def suggest_rig_views(self, n=3, cameras=None, reference=None, board=0, candidates=None, focus_grid=(16, 12), focus_distance=None,
+                        criterion="focus", min_cameras=2, hold=None, sigma2=None):
+    """Where to hold board `board` next so that the RIG gets better: the n candidate views that, one after the other, reduce most
+    the RMS transfer uncertainty from camera `reference` (None: the first of the group) into every other camera of the group
+    `cameras` (indices; None: all) over the focus grid at `focus_distance` (criterion="focus"), or carry the most information on
+    the group's intrinsics and camera poses together (criterion="gain"), under `covariance(hold, sigma2)` (multical_amd.guidance,
+    one covariance and one device call).  A candidate is a static capture in a new frame with a free rig pose, seen by every camera
+    of the group whose image it falls into, at least `min_cameras` of them; candidates: None (guidance.rig_candidate_poses) or poses
+    [m, 4, 4] board in rig.  focus_distance=None: the median distance of the candidates' board centres from the reference camera
+    (reported).  A group whose joint factor has more than guidance.RIG_MAX_R = 128 columns is refused: pass a smaller cameras=.
+    Returns struct(cameras, reference, focus_distance, poses [n, 4, 4] board in rig, camera_poses_of_board [n, C', 4, 4] board in
+    each camera of the group, candidate_index [n], gain [n] (nats, each conditional on the earlier picks), focus_rms_before,
+    focus_rms_after [n] (px), n_cameras [n], n_visible [n, C'], status (guidance.OK / TOO_FEW / UNCONSTRAINED), candidates, scores,
+    sigma2, dof)."""
+    from . import guidance
+    cov = self.covariance(hold=hold, sigma2=sigma2)
+    camera_index, pose_index = self._shared_layout()
+    rtvecs = np.asarray(self.camera_poses.params, dtype=np.float64).reshape(-1, 6)
+    out = guidance.suggest_rig_views(list(self.cameras), np.asarray(self.camera_poses.poses), cov, camera_index, pose_index,
+                                     list(self.boards), n=n, group=cameras, reference=reference, board=board, candidates=candidates,
+                                     focus_grid=focus_grid, focus_distance=focus_distance, criterion=criterion, min_cameras=min_cameras,
+                                     rtvecs=rtvecs, boards_free=self.optimize["boards"] is True)
+    return out._extend(sigma2=cov.sigma2, dof=cov.dof)
+
+  def report_rig_view_suggestions(self, stage="", n=3, board=0, criterion="focus", cameras=None, reference=None):
+    """One line per pick through the "calibration" logger: which cameras see it (with their corner counts), the distance of the
+    board's centre from the reference camera, its tilt against that camera's optical axis, the information gain and the focus RMS
+    (transfer uncertainty from the reference camera) before -> after the pick in px."""
+    from . import guidance
+    s = self.suggest_rig_views(n=n, board=board, criterion=criterion, cameras=cameras, reference=reference)
+    names = getattr(self.camera_poses, "names", None) or [f"cam{i}" for i in range(self.size.cameras)]
+    if s.status != guidance.OK:
+      why = "a parameter of the group is unconstrained" if s.status == guidance.UNCONSTRAINED else "no candidate is seen by enough cameras"
+      info(f"{stage} rig view: none suggested ({why})")
+      return s
+    pts = np.asarray(self.boards[board].adjusted_points, dtype=np.float64).reshape(-1, 3)
+    centre = 0.5 * (pts.min(axis=0) + pts.max(axis=0))
+    ia = list(s.cameras).index(s.reference)
+    before = float(s.focus_rms_before)
+    for k in range(n):
+      if s.candidate_index[k] < 0:
+        break
+      T = s.camera_poses_of_board[k, ia]
+      X = T[:3, :3] @ centre + T[:3, 3]
+      tilt = float(np.degrees(np.arccos(np.clip(abs(T[2, 2]), 0.0, 1.0))))
+      seen = ", ".join(f"{names[c]} ({int(m)})" for c, m in zip(s.cameras, s.n_visible[k]) if m > 0)
+      after = float(s.focus_rms_after[k])
+      info(f"{stage} rig view {k + 1}: seen by {seen}; board at distance={float(np.linalg.norm(X)):.3f} from {names[s.reference]}, "
+           f"tilt={tilt:.0f} deg, gain={float(s.gain[k]):.3f} nats, transfer RMS at {s.focus_distance:.3f} {before:.4f} -> {after:.4f} px")
+      before = after
+    return s
+
 
 def split_std(calib, std):
   """A vector over calib.param_vec (standard deviations) split into the enabled blocks: camera_poses [C, 6], board_poses

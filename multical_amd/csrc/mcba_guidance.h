@@ -72,10 +72,11 @@ MCBA_HD bool view_point(const double* crec, const double* vrec, const double* bo
   return true;
 }
 
-// the two rows of point i, r + nn entries each, written to row_u / row_v (LDS on the device); false: not visible, the rows are 0
-MCBA_HD bool point_rows(const double* crec, const double* vrec, const double* board_points, int board_stride, const double* uv_lists,
-                        int i, int r, int nn, double* row_u, double* row_v) {
-  double Y[3], rho = 0.0, uv[2], A[6], K[2 * KI];
+// point i of a view where a camera sees it: the scaled point Y, rho, A = d(u, v) / dY and Kc padded to 2 x KI; false: not visible
+// (in front, the projection finite, det d(u, v) / d(x, y) > 0 where it lands, a board's point inside the image by the margin)
+MCBA_HD bool visible_point(const double* crec, const double* vrec, const double* board_points, int board_stride, const double* uv_lists,
+                           int i, double* Y, double& rho, double* A, double* K) {
+  double uv[2];
   bool visible = view_point(crec, vrec, board_points, board_stride, uv_lists, i, Y, rho);
   if (visible) visible = uncertainty::project_padded(crec, Y, uv, A, K);
   if (visible) visible = undistort::finite_d(uv[0]) && undistort::finite_d(uv[1]) && A[0] * A[4] - A[1] * A[3] > 0.0;
@@ -83,6 +84,32 @@ MCBA_HD bool point_rows(const double* crec, const double* vrec, const double* bo
     const double m = crec[CREC_MARGIN];
     visible = uv[0] >= m && uv[1] >= m && uv[0] <= crec[CREC_W_IMG] - 1.0 - m && uv[1] <= crec[CREC_H_IMG] - 1.0 - m;
   }
+  return visible;
+}
+
+// the columns of a left rotation and of a translation of the point: A (e_k x Y), rho A e_k (three entries of each row)
+MCBA_HD void rotation_columns(const double* A, const double* Y, double* row_u, double* row_v) {
+  // e_0 x Y = (0, -Y2, Y1), e_1 x Y = (Y2, 0, -Y0), e_2 x Y = (-Y1, Y0, 0)
+  row_u[0] = A[2] * Y[1] - A[1] * Y[2];
+  row_v[0] = A[5] * Y[1] - A[4] * Y[2];
+  row_u[1] = A[0] * Y[2] - A[2] * Y[0];
+  row_v[1] = A[3] * Y[2] - A[5] * Y[0];
+  row_u[2] = A[1] * Y[0] - A[0] * Y[1];
+  row_v[2] = A[4] * Y[0] - A[3] * Y[1];
+}
+MCBA_HD void translation_columns(const double* A, double rho, double* row_u, double* row_v) {
+  MCBA_UNROLL
+  for (int k = 0; k < 3; ++k) {
+    row_u[k] = rho * A[k];
+    row_v[k] = rho * A[3 + k];
+  }
+}
+
+// the two rows of point i, r + nn entries each, written to row_u / row_v (LDS on the device); false: not visible, the rows are 0
+MCBA_HD bool point_rows(const double* crec, const double* vrec, const double* board_points, int board_stride, const double* uv_lists,
+                        int i, int r, int nn, double* row_u, double* row_v) {
+  double Y[3], rho = 0.0, A[6], K[2 * KI];
+  const bool visible = visible_point(crec, vrec, board_points, board_stride, uv_lists, i, Y, rho, A, K);
   if (!visible) {
     MCBA_NOUNROLL
     for (int j = 0; j < r + nn; ++j) row_u[j] = row_v[j] = 0.0;
@@ -106,22 +133,8 @@ MCBA_HD bool point_rows(const double* crec, const double* vrec, const double* bo
     MCBA_UNROLL
     for (int k = 0; k < 3; ++k) Y[k] -= vrec[V_CENTRE + k];
   }
-  if (nn >= 3) {
-    // A (e_k x Y): e_0 x Y = (0, -Y2, Y1), e_1 x Y = (Y2, 0, -Y0), e_2 x Y = (-Y1, Y0, 0)
-    row_u[r] = A[2] * Y[1] - A[1] * Y[2];
-    row_v[r] = A[5] * Y[1] - A[4] * Y[2];
-    row_u[r + 1] = A[0] * Y[2] - A[2] * Y[0];
-    row_v[r + 1] = A[3] * Y[2] - A[5] * Y[0];
-    row_u[r + 2] = A[1] * Y[0] - A[0] * Y[1];
-    row_v[r + 2] = A[4] * Y[0] - A[3] * Y[1];
-  }
-  if (nn == 6) {
-    MCBA_UNROLL
-    for (int k = 0; k < 3; ++k) {
-      row_u[r + 3 + k] = rho * A[k];
-      row_v[r + 3 + k] = rho * A[3 + k];
-    }
-  }
+  if (nn >= 3) rotation_columns(A, Y, row_u + r, row_v + r);
+  if (nn == 6) translation_columns(A, rho, row_u + r + 3, row_v + r + 3);
   return true;
 }
 

@@ -1,6 +1,7 @@
 // mcba_guidance_kernels.h -- the kernels of mcba_guidance.h.
 //
-// k_view_schur: ONE WORKGROUP OF 128 THREADS PER VIEW (candidate or focus), two waves.  The records of the view and of its camera
+// k_view_schur: ONE WORKGROUP OF 128 THREADS PER VIEW (candidate or focus), two waves; the staging of the rows and the MFMA accumulation
+// are wave_gram_tiles of mcba_gram_front.h, which k_rig_gram (mcba_rigview_kernels.h) shares.  The records of the view and of its camera
 // (entry, image size, W_c) are staged in LDS and read at uniform addresses; the camera-family switch is uniform over the workgroup.
 //   * a wave takes the view's points in chunks of 64, round-robin; lane l owns point l of the chunk: visibility, one projection
 //     (project_padded), the two rows [Kc W_c | E] of r + n_nuisance <= 24 entries, written straight to LDS at a 25-double stride
@@ -23,7 +24,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mcba_guidance.h"
-#include "mcba_pnp_kernels.h"
+#include "mcba_gram_front.h"
 
 namespace mcba {
 namespace guidance {
@@ -56,12 +57,9 @@ struct ScoreArgs {
   double* posterior;             // [C][rs][rs] or null
 };
 
-constexpr int SCHUR_THREADS = 128, SCHUR_WAVES = SCHUR_THREADS / 64;
-constexpr int LDV = 25, STAGE = 128 * LDV + 8;
 // LDS of k_view_schur, in doubles
 constexpr int L_CREC = 0, L_VREC = L_CREC + CREC_STRIDE, L_STAGE = L_VREC + V_STRIDE, L_G = L_STAGE + SCHUR_WAVES * STAGE,
               L_L = L_G + GS * GS, L_Y = L_L + MAX_NN * MAX_NN, L_SC = L_Y + MAX_NN * MAX_R, L_END = L_SC + 8;
-static_assert(GS * GS <= STAGE, "a wave's Gram tiles reuse its staging buffer");
 static_assert(MAX_COLS < LDV && LDV + 7 <= GS, "the columns a row holds, and what the second operand reads past it");
 static_assert((size_t)L_END * sizeof(double) <= 65536, "static LDS of k_view_schur");
 
@@ -79,41 +77,9 @@ __global__ __launch_bounds__(SCHUR_THREADS) void k_view_schur(SchurArgs a) {
   const double* vrec = lds + L_VREC;
   const int r = (int)crec[CREC_RANK], nn = (int)vrec[V_NN], n = (int)vrec[V_N], cols = r + nn;
   double* V = lds + L_STAGE + wave * STAGE;
-  const int rsub = lane >> 4, csub = lane & 15;
-  pnp::wave_double4 acc00 = {0.0, 0.0, 0.0, 0.0}, acc01 = acc00, acc11 = acc00;
-  int count = 0;
-  for (int base = wave * 64; base < n; base += SCHUR_THREADS) {          // (uniform over the wave)
-    const int i = base + lane;
-    double* row_u = V + (2 * lane) * LDV;
-    double* row_v = row_u + LDV;
-    bool visible = false;
-    if (i < n) {
-      visible = point_rows(crec, vrec, a.board_points, a.board_stride, a.uv, i, r, nn, row_u, row_v);
-    } else {
-      for (int j = 0; j < cols; ++j) row_u[j] = row_v[j] = 0.0;
-    }
-    count += __popcll(__ballot(visible));
-    pnp::wave_fence();
-    const int rows = 2 * min(64, n - base), nsteps = (rows + 3) >> 2;
-    const double* vp = V + rsub * LDV + csub;
-    for (int st = 0; st < nsteps; ++st) {
-      const double a0 = vp[(4 * st) * LDV];
-      acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, a0, acc00, 0, 0, 0);
-      if (cols > 16) {
-        const double a1 = vp[(4 * st) * LDV + 16];
-        acc01 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, a1, acc01, 0, 0, 0);
-        acc11 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, a1, acc11, 0, 0, 0);
-      }
-    }
-    pnp::wave_fence();
-  }
-  // the wave's tiles take the place of its staged rows: entry (i, j), i <= j, at V[i GS + j]
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    V[(rsub + 4 * q) * GS + csub] = acc00[q];
-    V[(rsub + 4 * q) * GS + 16 + csub] = acc01[q];
-    V[(16 + rsub + 4 * q) * GS + 16 + csub] = acc11[q];
-  }
+  const int count = wave_gram_tiles(V, n, cols, wave, lane, [&](int i, double* row_u, double* row_v) {
+    return point_rows(crec, vrec, a.board_points, a.board_stride, a.uv, i, r, nn, row_u, row_v);
+  });
   if (lane == 0) lds[L_SC + wave] = (double)count;
   __syncthreads();
   double* G = lds + L_G;
