@@ -825,6 +825,42 @@ int32_t mcba_rig_view_information(const mcba_camera_set* cams, const double* cam
  * rounds with their transfers (HIP events), [2] downloads, [3] the whole call; *n_slots (or NULL) = (view, camera) slots launched */
 int32_t mcba_debug_rig_view_information_ms(double* ms /*[4]*/, int64_t* n_slots);
 
+/* --- residual field: the systematic part of the reprojection error ------------------------ */
+/* Gram matrices of a smooth vector field fitted to the residuals as a function of the OBSERVED pixel.  Not part of the reference.
+ *   - model: per camera a tensor-product uniform cubic B-spline field e(u, v) in R^2 over [0, W] x [0, H] with nx x ny intervals:
+ *     K = (nx + 3)(ny + 3) control points, control point (a along y, b along x) in column a (nx + 3) + b, both components on the
+ *     same grid.  A pixel in interval (ix, iy) = floor(u nx / W), floor(v ny / H) (the far edge in the last interval, fraction 1)
+ *     has 16 non-zero weights wy[a] wx[b] >= 0 on the control points (iy + a, ix + b), a, b = 0 .. 3, which sum to 1; wx, wy are
+ *     the cubic B-spline weights ((1 - t)^3, 3 t^3 - 6 t^2 + 4, -3 t^3 + 3 t^2 + 3 t + 1, t^3) / 6 of the fraction t.
+ *   - row of an observation: [ b(u, v) (K entries) | r_x | r_y ],  r = projected - observed (the residual of mcba_residuals /
+ *     mcba_observation_covariance; rolling shutter: scan time from the observed row, as in mcba_project), NC = K + 2 columns.
+ *   - rows: every slot (c, f, b, p) of the mask mcba_reprojection_error returns as `valid` -- only the inliers among them if
+ *     inliers_only != 0 -- whose observed pixel lies in the closed image rectangle; the others of these slots are counted in
+ *     outside[c].  Weights are 0 / 1.
+ *   - gram [C][n_folds][NC][NC]: the sum of row^T row over the rows of camera c in the frames f with f mod n_folds == fold: B^T B
+ *     (K x K), B^T r_x, B^T r_y (columns K, K + 1), r_x^T r_x, r_x^T r_y, r_y^T r_y; full symmetric storage, the two triangles
+ *     equal to the bit.  A fold without frames or rows is exactly zero.  count [C][n_folds]: its rows.  Summed in a fixed order:
+ *     two calls on one handle return the same bytes.
+ *   - coverage [C][2][cov_h][cov_w] (or NULL; 1 <= cov_w cov_h <= 512): valid slots inside the image per cell (ix, iy) =
+ *     floor(u cov_w / W), floor(v cov_h / H) of the observed pixel, plane 0 the inliers, plane 1 the valid slots that are not
+ *     (whatever inliers_only says).
+ *   - refused with a message: a frame-sharded handle; nx, ny or n_folds below 1; n_folds > 16; NC > 64 (nx = 6, ny = 4 has
+ *     K = 63); an image size that is not positive.  Handles with the `boards` block optimised are fine.
+ * One pass over the observation table on the device (csrc/mcba_residual_field_kernels.h): the table evaluation and k_residual of
+ * mcba_project, then one wavefront per (camera, fold, frame chunk) accumulating the upper 16 x 16 tiles by FP64 MFMA and a fold of
+ * the chunk partials.  Only the blocks, the counts and the maps leave the device.  x is not changed, nor is any other state
+ * a later call reads.                                                                                                            */
+int32_t mcba_residual_gram(mcba_handle h, const double* x, const int32_t* image_size /*[C][2] W,H*/,
+                           int32_t nx, int32_t ny, int32_t n_folds, int32_t inliers_only,
+                           double* gram      /*[C][n_folds][NC][NC], full symmetric*/,
+                           int64_t* count    /*[C][n_folds] rows that entered*/,
+                           int64_t* outside  /*[C] slots skipped: observed pixel outside the image*/,
+                           int32_t cov_w, int32_t cov_h,
+                           int32_t* coverage /*[C][2][cov_h][cov_w]: inliers | valid but rejected; may be NULL*/);
+/* timing of the last mcba_residual_gram call of this thread, milliseconds: [0] the projection pass (table evaluation + k_residual),
+ * [1] k_residual_gram, [2] k_residual_gram_fold (HIP events), [3] the whole call; *n_rows (or NULL) = rows that entered           */
+int32_t mcba_debug_residual_gram_ms(double* ms /*[4]*/, int64_t* n_rows);
+
 /* --- solve -------------------------------------------------------------------------------------------------- */
 /* Trust-region least squares: replaces scipy.optimize.least_squares(method='trf', x_scale='jac', jac_sparsity=S,
  * loss, f_scale, ftol, max_nfev) at calibration.py:209-210.  x is updated in place to `res.x`.                 */

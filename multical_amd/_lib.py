@@ -252,6 +252,9 @@ SYMBOLS = [
                                               c_double_p, C.POINTER(C.c_int64), c_double_p]),
   ("mcba_debug_observation_covariance_ms", C.c_int32, [H, c_double_p]),
   ("mcba_debug_set_observation_covariance_route", C.c_int32, [H, C.c_int32]),
+  ("mcba_residual_gram", C.c_int32, [H, c_double_p, c_int32_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p,
+                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int32, c_int32_p]),
+  ("mcba_debug_residual_gram_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_solve", C.c_int32, [H, c_double_p, C.POINTER(Options), C.POINTER(Result)]),
   ("mcba_time_linearize", C.c_int32, [H, c_double_p, C.POINTER(Options), C.c_int32, c_double_p]),
   ("mcba_time_residuals", C.c_int32, [H, c_double_p, C.c_int32, c_double_p]),

@@ -383,6 +383,29 @@ class Handle(object):
     check(self.lib.mcba_debug_observation_covariance_ms(self.h, C.byref(ms)))
     return ms.value
 
+  def residual_gram(self, x, image_size, nx=5, ny=4, n_folds=5, inliers_only=True, coverage=(16, 12)):
+    """Gram matrices of the residual-field rows [b(u, v) | r_x | r_y] per (camera, fold = frame mod n_folds) at x
+    (mcba_residual_gram; multical_amd.residual_field does the algebra).  image_size [C, 2] (W, H); coverage=(w, h) or None.
+    Returns struct(gram [C, n_folds, NC, NC], count [C, n_folds], outside [C], coverage [C, 2, h, w] or None), NC = (nx + 3)(ny + 3) + 2."""
+    from .structs import struct
+    x = self._x(x)
+    n_cam = int(self.shape[0])
+    size = np.ascontiguousarray(np.asarray(image_size, dtype=np.int32).reshape(-1, 2))
+    assert size.shape == (n_cam, 2), f"image_size is {size.shape}, not {(n_cam, 2)}"
+    nx, ny, n_folds = int(nx), int(ny), int(n_folds)
+    # (the library refuses bad arguments with its own messages before it writes anything: a refused call gets token outputs)
+    nc = (nx + 3) * (ny + 3) + 2
+    bad = nx < 1 or ny < 1 or not 1 <= n_folds <= 16 or nc > 64
+    gram = np.zeros(1 if bad else (n_cam, n_folds, nc, nc))
+    count = np.zeros(1 if bad else (n_cam, n_folds), dtype=np.int64)
+    outside = np.zeros(n_cam, dtype=np.int64)
+    cw, ch = (0, 0) if coverage is None else (int(coverage[0]), int(coverage[1]))
+    cov = None if coverage is None else np.zeros((n_cam, 2, max(ch, 1), max(cw, 1)), dtype=np.int32)
+    check(self.lib.mcba_residual_gram(self.h, _ptr(x, C.c_double), _ptr(size, C.c_int32), nx, ny, n_folds, 1 if inliers_only else 0,
+                                      _ptr(gram, C.c_double), _ptr(count, C.c_int64), _ptr(outside, C.c_int64), cw, ch,
+                                      None if cov is None else _ptr(cov, C.c_int32)))
+    return struct(gram=gram, count=count, outside=outside, coverage=cov)
+
   def debug_gn_step(self, reg):
     gn = np.empty(self.n_params)
     gh = np.empty(self.n_params)

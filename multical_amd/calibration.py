@@ -625,6 +625,40 @@ class Calibration(parameters.Parameters):
       info(f"{stage} {names[c]}: predicted std median={med:.4f} max={float(oc.cam_max_std[c]):.4f} px, "
            f"max leverage={float(l.max()) if l.size else float('nan'):.4f}")
 
+  # --- residual fields: the systematic part of the reprojection error ----------------------------
+  def residual_field(self, nx=5, ny=4, n_folds=5, prior_px=1.0, sigma2=None, inliers_only=True, grid=(16, 12), pixels=None,
+                     coverage=(16, 12), tau0=100.0):
+    """Is what the bundle adjustment leaves behind noise?  Per camera a smooth vector field (uniform cubic B-spline, nx x ny
+    intervals over the image) is fitted to the residuals projected - observed as a function of the observed pixel: one pass over the
+    observation table on the device (mcba_residual_gram), the rest numpy on blocks of at most 62 x 62 (multical_amd.residual_field).
+    Returns struct(field [C, gh, gw, 2] on the centres of `grid` (or [C, n, 2] at `pixels`), field_std (its posterior standard
+    deviation), pixels, coefficients [C, K, 2], n, rms (all of the residual), systematic_rms (the fitted field at the observations),
+    explained (in-sample), cv_gain (share of the squared error of held-out frames, fold = frame mod n_folds, that the field
+    predicts; about 0 or negative for noise), z (energy of the fit against sigma2, in standard deviations), T, nu, count
+    [C, n_folds], outside [C] (observed pixels outside the image), coverage [C, 2, h, w] (inliers | valid but rejected), sigma2).
+    Modelling choices: prior_px = the second difference of neighbouring control values thought plausible (1 px); tau0 = 100 px only
+    keeps the system positive definite where a camera never saw a board; sigma2 = the residual variance (None: the estimate
+    `covariance` uses).  Always the plain (unsharded) handle."""
+    from . import residual_field
+    if sigma2 is None:
+      sigma2 = self.covariance().sigma2
+    sizes = [tuple(int(v) for v in cam.image_size) for cam in self.cameras]
+    g = self._handle().residual_gram(self.param_vec, sizes, nx=nx, ny=ny, n_folds=n_folds, inliers_only=inliers_only,
+                                     coverage=coverage)
+    return residual_field.analyse(g.gram, g.count, g.outside, g.coverage, sizes, int(nx), int(ny), sigma2, prior_px=prior_px,
+                                  tau0=tau0, grid=grid, pixels=pixels)
+
+  def report_residual_field(self, stage="", **kwargs):
+    """One line per camera through the "calibration" logger: n, rms, systematic_rms, cv_gain, z, the largest |field| on the grid and
+    where it is.  A camera whose cv_gain exceeds 0.1 AND whose z exceeds 5 gets a warning instead: both thresholds are reporting
+    conventions (residual_field.WARN_CV_GAIN, WARN_Z), not tests.  Returns the result of `residual_field(**kwargs)`."""
+    from . import residual_field
+    out = self.residual_field(**kwargs)
+    names = getattr(self.camera_poses, "names", None) or [f"cam{i}" for i in range(self.size.cameras)]
+    for line, warn in residual_field.report_lines(out, names, stage):
+      (logger.warning if warn else info)(line)
+    return out
+
 
   # --- triangulation through the rig (DESIGN.md 3.12) --------------------------------------------------------------
   @cached_property

@@ -21,6 +21,7 @@
 #include "mcba_solver_kernels.h"
 #include "mcba_cov_kernels.h"
 #include "mcba_obscov_kernels.h"
+#include "mcba_residual_field_kernels.h"
 #include "mcba_host.h"
 
 using namespace mcba;
@@ -158,6 +159,10 @@ struct mcba_handle_s {
   DevBuf<double> oc_cov, oc_student, oc_part, oc_out, oc_g;   // oc_g: Q [views][DF + ns][NG] of k_obscov_whiten
   double oc_pass_ms = 0.0;
   bool oc_sigma_route = false;   // debug (mcba_debug_set_observation_covariance_route): force the Sigma-route fallback (tests)
+  // mcba_residual_gram: image sizes, per-chunk partials and their integer counts, {gram | count | outside | coverage} results
+  DevBuf<int32_t> rf_size, rf_cov;
+  DevBuf<double> rf_part, rf_gram;
+  DevBuf<long long> rf_cpart, rf_count;
   int lin_grid = 0;          // 0 = automatic (see linearize, mcba_cam_impl.h), > 0 = forced number of persistent workgroups (debug)
 
   int64_t n_inliers = 0;               // inliers of this shard
@@ -1817,6 +1822,100 @@ int32_t mcba_debug_observation_covariance_ms(mcba_handle h, double* ms) {
   API_BEGIN
   REQUIRE(h && ms, "null argument");
   *ms = h->oc_pass_ms;
+  API_END
+}
+
+// ---- residual field: the Gram matrices of the rows [b(u, v) | r_x | r_y] per (camera, fold) ----------------------
+// slots: [0] projection pass (table evaluation + k_residual), [1] k_residual_gram, [2] k_residual_gram_fold (HIP events), [3] the
+// whole call by host clock; count = rows that entered
+MCBA_TIMING_GETTER(mcba_debug_residual_gram_ms, g_resfield_timing, 4)
+
+namespace {
+struct EventSet {   // timing events of one call
+  hipEvent_t ev[4] = {};
+  EventSet() { for (hipEvent_t& e : ev) HIP_OK(hipEventCreate(&e)); }
+  EventSet(const EventSet&) = delete;
+  ~EventSet() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+}  // namespace
+
+int32_t mcba_residual_gram(mcba_handle h, const double* x, const int32_t* image_size, int32_t nx, int32_t ny, int32_t n_folds,
+                           int32_t inliers_only, double* gram, int64_t* count, int64_t* outside, int32_t cov_w, int32_t cov_h,
+                           int32_t* coverage) {
+  API_BEGIN
+  using namespace mcba::resfield;
+  REQUIRE(h && x && image_size && gram && count && outside, "null argument");
+  const double t_call = now_seconds();
+  g_fill_stream = h->stream;
+  const Dims& d = h->d;
+  REQUIRE(d.shard_world == 0 && d.f0 == 0 && d.Fl == d.F, "residual field: a frame-sharded handle is not supported (use a plain handle)");
+  REQUIRE(nx >= 1 && ny >= 1, "residual field: nx and ny must be at least 1");
+  REQUIRE(n_folds >= 1, "residual field: n_folds must be at least 1");
+  REQUIRE(n_folds <= MAX_FOLDS, "residual field: at most " + std::to_string(MAX_FOLDS) + " folds are supported");
+  REQUIRE(nx <= MAX_NC && ny <= MAX_NC && n_control(nx, ny) + 2 <= MAX_NC,
+          "residual field: " + std::to_string(nx) + " x " + std::to_string(ny) + " intervals need more than " +
+              std::to_string(MAX_NC) + " columns (control points + 2)");
+  for (int c = 0; c < d.C; ++c)
+    REQUIRE(image_size[2 * c] > 0 && image_size[2 * c + 1] > 0,
+            "residual field: the image size of camera " + std::to_string(c) + " is not positive");
+  if (coverage)
+    REQUIRE(cov_w >= 1 && cov_h >= 1 && (int64_t)cov_w * cov_h <= MAX_COV_BINS,
+            "residual field: a coverage map has between 1 and " + std::to_string(MAX_COV_BINS) + " cells");
+  const int NC = n_control(nx, ny) + 2, NT = (NC + 15) / 16, nck = d.C * n_folds, nch = gram_chunks(d.C, d.F, n_folds);
+  const size_t nref = (size_t)d.C * d.F * d.B * d.P, ngram = (size_t)nck * NC * NC;
+  const size_t ncov = coverage ? (size_t)d.C * 2 * cov_w * cov_h : 0;
+  EventSet es;
+  // the projected points [C,F,B,P,2], the per-slot errors and the valid mask [C,F,B,P], as mcba_project / mcba_reprojection_error
+  h->out_big.alloc(3 * nref, true);
+  h->out_valid.alloc(nref, true);
+  h->rf_size.alloc(2 * (size_t)d.C, false);
+  h->rf_part.alloc((size_t)nck * nch * RG_PART, false);
+  h->rf_cpart.alloc(2 * (size_t)nck * nch, false);
+  h->rf_gram.alloc(ngram, true);
+  h->rf_count.alloc((size_t)nck + d.C, true);   // [count | outside]
+  if (coverage) h->rf_cov.alloc(ncov, true);
+  HIP_OK(hipMemcpyAsync(h->rf_size.p, image_size, 2 * (size_t)d.C * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  upload_x(h, x, h->x.p);
+  HIP_OK(hipEventRecord(es.ev[0], h->stream));
+  eval_tables(h, h->x.p);
+  h->ops->residual(d, h->t, h->stream, nullptr, nullptr, h->out_big.p, h->out_big.p + 2 * nref, h->out_valid.p);
+  HIP_OK(hipEventRecord(es.ev[1], h->stream));
+  GramArgs a{};
+  a.proj = h->out_big.p;
+  a.valid = h->out_valid.p;
+  a.obs = h->obs.p;
+  a.inlier = h->inlier.p;
+  a.image_size = h->rf_size.p;
+  a.C = d.C, a.F = d.F, a.BP = d.B * d.P;
+  a.nx = nx, a.ny = ny, a.n_folds = n_folds, a.nch = nch, a.inliers_only = inliers_only != 0;
+  a.cov_w = coverage ? cov_w : 0, a.cov_h = coverage ? cov_h : 0;
+  a.part = h->rf_part.p;
+  a.cpart = h->rf_cpart.p;
+  a.coverage = coverage ? h->rf_cov.p : nullptr;
+  const dim3 grid(nck * nch), block(64);
+  if (NT <= 2) hipLaunchKernelGGL((k_residual_gram<2>), grid, block, 0, h->stream, a);
+  else if (NT == 3) hipLaunchKernelGGL((k_residual_gram<3>), grid, block, 0, h->stream, a);
+  else hipLaunchKernelGGL((k_residual_gram<4>), grid, block, 0, h->stream, a);
+  HIP_OK(hipEventRecord(es.ev[2], h->stream));
+  hipLaunchKernelGGL(k_residual_gram_fold, dim3(nck, NT * (NT + 1) / 2), dim3(256), 0, h->stream, a, h->rf_gram.p, h->rf_count.p,
+                     reinterpret_cast<unsigned long long*>(h->rf_count.p + nck));
+  HIP_OK(hipEventRecord(es.ev[3], h->stream));
+  check_launch("residual field kernels");
+  std::vector<long long> counts((size_t)nck + d.C);
+  HIP_OK(hipMemcpyAsync(gram, h->rf_gram.p, ngram * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipMemcpyAsync(counts.data(), h->rf_count.p, counts.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  if (coverage) HIP_OK(hipMemcpyAsync(coverage, h->rf_cov.p, ncov * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  sync(h);
+  int64_t n_rows = 0;
+  for (int i = 0; i < nck; ++i) n_rows += (count[i] = (int64_t)counts[i]);
+  for (int c = 0; c < d.C; ++c) outside[c] = (int64_t)counts[(size_t)nck + c];
+  g_resfield_timing.reset(n_rows);
+  for (int i = 0; i < 3; ++i) {
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, es.ev[i], es.ev[i + 1]));
+    g_resfield_timing.ms[i] = (double)ms;
+  }
+  g_resfield_timing.ms[3] = (now_seconds() - t_call) * 1e3;
   API_END
 }
 
