@@ -861,6 +861,46 @@ int32_t mcba_residual_gram(mcba_handle h, const double* x, const int32_t* image_
  * [1] k_residual_gram, [2] k_residual_gram_fold (HIP events), [3] the whole call; *n_rows (or NULL) = rows that entered           */
 int32_t mcba_debug_residual_gram_ms(double* ms /*[4]*/, int64_t* n_rows);
 
+/* --- applying the residual field: corrected points, maps and images ------------------------------------------------- */
+/* The fitted field as a warp of the image plane (csrc/mcba_warp.h).  Definitions -- they decide every sign:
+ *   - field: e_c(u, v) = sum_k b_k(u, v) coef[c][k][:], grid nx x ny over the image (W_c, H_c), control point (a, b) (a along y, b
+ *     along x) in column a (nx + 3) + b -- the coefficients of the fit of mcba_residual_gram's rows, r = projected - observed as a
+ *     function of the observed pixel.  Outside the closed image rectangle the field is that of the pixel clamped to it.
+ *   - forward warp, raw -> corrected: w(p) = p + e(p): the corrected observation is what the parametric model predicts.
+ *   - inverse warp, corrected -> raw: p + e(p) = q by Newton (analytic Jacobian I + De, start q - e(q), stop at max |dp| <= 1e-11 px
+ *     or a step that no longer moves p, at most 50 steps): status MCBA_UNDISTORT_OK / MCBA_UNDISTORT_NOT_CONVERGED (NaN).  A
+ *     non-finite input gives NaN and NOT_CONVERGED in both directions.
+ *   - fold bound: L = max over the two components of max |D_x coef| nx / W + max |D_y coef| ny / H (D: first difference of
+ *     neighbouring control values) bounds the infinity norm of De.  Below 0.2 Newton contracts by 2 L / (1 - L) <= 0.5 a step from
+ *     any start, so a finite input always converges; a field set with L >= 0.2 is refused ("the field folds the image").
+ *   - corrected camera: project_corrected(X) = w^-1(pi(X)), undistort_corrected(p) = pi^-1(w(p)); a corrected map holds
+ *     w^-1(pi(iR [u v 1])) of every destination pixel, FP64 throughout and rounded once to float32.
+ * Handle-less, the error convention of the undistortion entries.  Refused with a message: a field set whose C differs from the
+ * camera set's; nx or ny below 1; (nx + 3)(ny + 3) > 62; an image size that is not positive; a coefficient that is not finite;
+ * L >= 0.2; a camera index out of range; the image-format refusals of mcba_undistort_images.                                     */
+typedef struct mcba_field_set {
+  int32_t C;                      /* cameras                                                                            */
+  const int32_t* image_size;      /* [C][2] W, H                                                                        */
+  int32_t nx, ny;                 /* intervals of the spline grid, the same for every camera                            */
+  const double* coef;             /* [C][(nx + 3)(ny + 3)][2]                                                           */
+} mcba_field_set;
+/* out [n,2] = w(uv) (inverse == 0) or w^-1(uv) (inverse != 0) through the field of camera_of_point[i] (NULL = camera 0); status [n]
+ * MCBA_UNDISTORT_*, or NULL.  A whole [C,F,B,P,2] observation table is one call over its flat list of slots.  n == 0 launches
+ * nothing.                                                                                                              */
+int32_t mcba_warp_points(const mcba_field_set* f, int64_t n, const int32_t* camera_of_point, int32_t inverse, const double* uv,
+                         double* out, uint8_t* status);
+/* mcba_undistort_maps of the corrected cameras: maps [C,height,width,2].  With an all-zero field the bytes of mcba_undistort_maps. */
+int32_t mcba_undistort_maps_corrected(const mcba_camera_set* cams, const mcba_field_set* f, const double* R, const double* P,
+                                      int32_t width, int32_t height, float* maps);
+/* mcba_undistort_images of the corrected cameras: the corrected maps are made in device memory the call owns and feed the map-fed
+ * remap kernel on the same stream -- byte for byte mcba_remap through mcba_undistort_maps_corrected; no map leaves the device.  */
+int32_t mcba_undistort_images_corrected(const mcba_camera_set* cams, const mcba_field_set* f, const double* R, const double* P,
+                                        const void* src, int32_t N, int32_t Hs, int32_t Ws, int32_t channels, int32_t dtype,
+                                        const int32_t* camera_of_image, int32_t Hd, int32_t Wd, double border, void* dst);
+/* timing of the last corrected call of this thread, milliseconds: [0] uploads, [1] the kernels (HIP events), [2] downloads, [3] the
+ * whole call; *n (or NULL) = points or pixels written                                                                   */
+int32_t mcba_debug_warp_ms(double* ms /*[4]*/, int64_t* n);
+
 /* --- solve -------------------------------------------------------------------------------------------------- */
 /* Trust-region least squares: replaces scipy.optimize.least_squares(method='trf', x_scale='jac', jac_sparsity=S,
  * loss, f_scale, ftol, max_nfev) at calibration.py:209-210.  x is updated in place to `res.x`.                 */

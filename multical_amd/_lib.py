@@ -84,6 +84,10 @@ class CameraSet(C.Structure):   # mcba_camera_set
               ("is_fisheye", c_uint8_p)]
 
 
+class FieldSet(C.Structure):   # mcba_field_set
+  _fields_ = [("C", C.c_int32), ("image_size", c_int32_p), ("nx", C.c_int32), ("ny", C.c_int32), ("coef", c_double_p)]
+
+
 class TriangulateProblem(C.Structure):   # mcba_triangulate_problem
   _fields_ = [("cams", CameraSet), ("F", C.c_int32), ("M", C.c_int64), ("views", c_double_p), ("views_end", c_double_p),
               ("image_heights", c_double_p), ("view_valid", c_uint8_p), ("points", c_double_p), ("valid", c_uint8_p),
@@ -255,6 +259,13 @@ SYMBOLS = [
   ("mcba_residual_gram", C.c_int32, [H, c_double_p, c_int32_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p,
                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int32, c_int32_p]),
   ("mcba_debug_residual_gram_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_warp_points", C.c_int32, [C.POINTER(FieldSet), C.c_int64, c_int32_p, C.c_int32, c_double_p, c_double_p, c_uint8_p]),
+  ("mcba_undistort_maps_corrected", C.c_int32, [C.POINTER(CameraSet), C.POINTER(FieldSet), c_double_p, c_double_p, C.c_int32, C.c_int32,
+                                                C.POINTER(C.c_float)]),
+  ("mcba_undistort_images_corrected", C.c_int32, [C.POINTER(CameraSet), C.POINTER(FieldSet), c_double_p, c_double_p, C.c_void_p,
+                                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_int32,
+                                                  C.c_double, C.c_void_p]),
+  ("mcba_debug_warp_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_solve", C.c_int32, [H, c_double_p, C.POINTER(Options), C.POINTER(Result)]),
   ("mcba_time_linearize", C.c_int32, [H, c_double_p, C.POINTER(Options), C.c_int32, c_double_p]),
   ("mcba_time_residuals", C.c_int32, [H, c_double_p, C.c_int32, c_double_p]),

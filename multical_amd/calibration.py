@@ -227,8 +227,16 @@ handle_cache = _HandleCache()
 
 
 class Calibration(parameters.Parameters):
+  correction = None          # a correction.FieldCorrection and the table it was applied to: with_corrected_observations
+  raw_point_table = None
+
   def __init__(self, cameras, boards, point_table, camera_poses, board_poses, motion, inlier_mask=None,
-               optimize=default_optimize):
+               optimize=default_optimize, correction=None, raw_point_table=None):
+    # (correction, raw_point_table: set by with_corrected_observations alone -- point_table is then the warped raw table)
+    assert (correction is None) == (raw_point_table is None), "a corrected calibration carries its raw table"
+    if correction is not None:            # (class attributes else: the state of an uncorrected calibration is what it was)
+      self.correction = correction
+      self.raw_point_table = raw_point_table
     self.cameras = cameras
     self.boards = boards
     self.point_table = point_table
@@ -280,6 +288,8 @@ class Calibration(parameters.Parameters):
 
   def __getstate__(self):
     attrs = ['cameras', 'boards', 'point_table', 'camera_poses', 'board_poses', 'motion', 'inlier_mask', 'optimize']
+    if self.correction is not None:
+      attrs = attrs + ['correction', 'raw_point_table']
     return subset(self.__dict__, attrs)
 
   def __setstate__(self, d):
@@ -659,6 +669,74 @@ class Calibration(parameters.Parameters):
       (logger.warning if warn else info)(line)
     return out
 
+  # --- applying the residual field -----------------------------------------------------------------
+  def _image_sizes(self):
+    return [tuple(int(v) for v in cam.image_size) for cam in self.cameras]
+
+  def _uncorrected(self):
+    """this calibration on its raw observation table, at the current parameters"""
+    if self.correction is None:
+      return self
+    d = self.__getstate__()
+    d.update(point_table=self.raw_point_table, correction=None, raw_point_table=None)
+    return Calibration(**d)
+
+  def residual_correction(self, **fit_kwargs):
+    """The correction.FieldCorrection of `residual_field(**fit_kwargs).coefficients`: the fitted field as a warp of the image plane,
+    w(p) = p + e(p), raw pixel -> the pixel the parametric model explains."""
+    from .correction import FieldCorrection
+    out = self.residual_field(**fit_kwargs)
+    return FieldCorrection(out.coefficients, self._image_sizes(), out.nx, out.ny)
+
+  def with_corrected_observations(self, correction):
+    """A copy whose point_table is the RAW observation table warped by `correction` (one device call, mcba_warp_points); it carries
+    `correction` and `raw_point_table`, and report, bundle_adjust, covariance, triangulate, localize and residual_field work on it
+    unchanged.  On an already corrected calibration the raw table is warped again, never a warp of a warp.  (A later
+    copy(point_table=...) keeps the attributes: replace the table through this method only.)"""
+    raw = self.point_table if self.correction is None else self.raw_point_table
+    return self.copy(point_table=correction.correct_table(raw), correction=correction, raw_point_table=raw)
+
+  def refine_with_residual_field(self, rounds=3, sigma2=None, **kwargs):
+    """Alternates, `rounds` times: (1) fit the field to the RAW residuals at the current parameters, (2) bundle_adjust on the raw
+    table corrected by that field.  nx, ny, n_folds, prior_px and tau0 go to the fit, every other keyword to bundle_adjust.  sigma2
+    is fixed at the first round (the caller's value or the `covariance()` estimate); the inlier mask, prior_px and tau0 are held.
+    Returns (the corrected calibration, one record per round: struct(sse, penalty, joint = sse + c^T Pen c, rms, systematic_rms,
+    cv_gain, z, param_vec)): sse of the corrected table's inliers after the round's adjustment, the per-camera figures of the
+    round's fit, param_vec the parameters the round's field was fitted at.
+
+    This is block coordinate descent on J(x, c) = |pi(x) - p - B c|^2 + c^T Pen c -- step (1) minimises over c exactly, step (2)
+    over x -- so `joint` cannot rise from round to round, PROVIDED: linear loss, a fixed inlier set, no observation outside the
+    image (there the field is the clamped extension, which the fit does not see) and a static motion model.  Under rolling shutter
+    the scan time is read from the CORRECTED row, so the two steps minimise slightly different functions."""
+    from . import residual_field as rf
+    from .correction import FieldCorrection
+    fit_kwargs = {k: kwargs.pop(k) for k in ("nx", "ny", "n_folds", "prior_px", "tau0") if k in kwargs}
+    assert int(rounds) >= 1, "refine_with_residual_field: at least one round"
+    if sigma2 is None:
+      sigma2 = self.covariance().sigma2
+    sigma2 = float(sigma2)
+    current, records = self, []
+    for _ in range(int(rounds)):
+      raw = current._uncorrected()
+      fit = raw.residual_field(sigma2=sigma2, **fit_kwargs)
+      correction = FieldCorrection(fit.coefficients, self._image_sizes(), fit.nx, fit.ny)
+      current = current.with_corrected_observations(correction).bundle_adjust(**kwargs)
+      r = np.asarray(current.residuals(), dtype=np.float64)
+      pen = rf.penalty(fit.nx, fit.ny, sigma2, fit.prior_px, fit.tau0)
+      sse, penalty = float(r @ r), float(np.einsum("cki,kl,cli->", fit.coefficients, pen, fit.coefficients))
+      records.append(struct(sse=sse, penalty=penalty, joint=sse + penalty, rms=fit.rms, systematic_rms=fit.systematic_rms,
+                            cv_gain=fit.cv_gain, z=fit.z, param_vec=np.array(raw.param_vec, dtype=np.float64)))
+    return current, records
+
+  def report_residual_correction(self, stage=""):
+    """One line per camera through the "calibration" logger: the fold bound of its field, the largest |e| on the default grid, the
+    reprojection rms of the camera's inliers on the raw and on the corrected table (both at the current parameters)."""
+    from . import correction
+    assert self.correction is not None, "report_residual_correction: this calibration carries no correction"
+    names = getattr(self.camera_poses, "names", None) or [f"cam{i}" for i in range(self.size.cameras)]
+    before, after = self._uncorrected().residual_field(sigma2=1.0).rms, self.residual_field(sigma2=1.0).rms
+    for line in correction.report_lines(self.correction, names, before, after, stage):
+      info(line)
 
   # --- triangulation through the rig (DESIGN.md 3.12) --------------------------------------------------------------
   @cached_property

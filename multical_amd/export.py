@@ -51,11 +51,17 @@ def export_json(calib, names, filenames, master=None):
   camera_names = list(names.camera if hasattr(names, "camera") else names["camera"])
   camera_poses = calib.camera_poses.pose_table
   filenames = [list(x) for x in zip(*filenames)] if len(filenames) else []   # structs.struct.transpose_lists
-  return dict(
+  data = dict(
     cameras=export_cameras(camera_names, calib.cameras),
     camera_poses=export_camera_poses(camera_names, camera_poses) if master is None
     else export_relative(camera_names, camera_poses, master),
     image_sets=export_images(camera_names, filenames))
+  # (no key of multical's format: written only for a calibration that carries a residual correction, DESIGN.md 3.19 -- its cameras
+  #  are the parametric part of the model, the field of camera i is entry i of `coefficients`)
+  correction = getattr(calib, "correction", None)
+  if correction is not None:
+    data["residual_correction"] = dict(correction.to_dict(), cameras=camera_names)
+  return data
 
 
 def export(filename, calib, names, filenames, master=None):

@@ -86,13 +86,21 @@ def import_camera_poses(data, names):
 
 def import_cameras(data, fisheye=None):
   """The cameras and camera poses of a decoded calibration.json: struct(names, cameras (Camera / CameraFisheye), camera_poses
-  [C, 4, 4] rig -> camera, in the order of the file).  fisheye: names (or a dict name -> bool) of the Kannala-Brandt cameras."""
+  [C, 4, 4] rig -> camera, in the order of the file; correction (a correction.FieldCorrection) if the file has a
+  `residual_correction` block).  fisheye: names (or a dict name -> bool) of the Kannala-Brandt cameras."""
   names = list(data["cameras"].keys())
   if fisheye is not None and not isinstance(fisheye, dict):
     fisheye = {n: n in set(fisheye) for n in names}
   cameras = [import_camera(data["cameras"][n], None if fisheye is None else bool(fisheye.get(n, False))) for n in names]
   poses = import_camera_poses(data.get("camera_poses", {}), names)
-  return struct(names=names, cameras=cameras, camera_poses=np.stack([poses[n] for n in names]))
+  out = struct(names=names, cameras=cameras, camera_poses=np.stack([poses[n] for n in names]))
+  if "residual_correction" in data:       # (written by multical_amd.export for a corrected calibration only: `correction` is absent else)
+    from .correction import FieldCorrection
+    block = data["residual_correction"]
+    if list(block.get("cameras", names)) != names:
+      raise ValueError(f"import_calib: the residual correction is for cameras {block['cameras']}, the file has {names}")
+    out = out._extend(correction=FieldCorrection.from_dict(block))
+  return out
 
 
 def load_calibration(filename, fisheye=None):

@@ -87,8 +87,12 @@ class ImageBatch(object):
     return out[..., 0] if self.grey else out
 
 
-def project_points(cameras, points, camera_of_point=None):
-  """mcba_project_points: pixels [n, 2] of camera-frame points [n, 3]; camera_of_point [n] indexes `cameras` (None: camera 0)."""
+def project_points(cameras, points, camera_of_point=None, correction=None):
+  """mcba_project_points: pixels [n, 2] of camera-frame points [n, 3]; camera_of_point [n] indexes `cameras` (None: camera 0).
+  correction (a correction.FieldCorrection): the corrected camera, w^-1 of the projection -- (pixels, status) of two device calls."""
+  if correction is not None:
+    from . import correction as _correction
+    return _correction.project_points(cameras, points, camera_of_point, correction)
   inp = CameraSetInputs(cameras)
   X = _f64(points).reshape(-1, 3)
   of = inp.index(camera_of_point, len(X))
@@ -98,9 +102,13 @@ def project_points(cameras, points, camera_of_point=None):
   return uv
 
 
-def undistort_points(cameras, pixels, camera_of_point=None, R=None, P=None):
+def undistort_points(cameras, pixels, camera_of_point=None, R=None, P=None, correction=None):
   """mcba_undistort_points: (out [n, 2], status [n]).  out = P [X/W, Y/W, 1] with [X Y W] = R [x y 1] of the undistorted normalised
-  point; P = None: the normalised point.  A pixel the model cannot have produced: NaN, status UNDISTORT_NOT_CONVERGED."""
+  point; P = None: the normalised point.  A pixel the model cannot have produced: NaN, status UNDISTORT_NOT_CONVERGED.
+  correction: the corrected camera, the forward warp of the pixels first (two device calls)."""
+  if correction is not None:
+    from . import correction as _correction
+    return _correction.undistort_points(cameras, pixels, camera_of_point, R, P, correction)
   inp = CameraSetInputs(cameras, R, P)
   uv = _f64(pixels).reshape(-1, 2)
   of = inp.index(camera_of_point, len(uv))
@@ -111,10 +119,14 @@ def undistort_points(cameras, pixels, camera_of_point=None, R=None, P=None):
   return out, status
 
 
-def undistort_maps(cameras, image_size, R=None, P=None):
+def undistort_maps(cameras, image_size, R=None, P=None, correction=None):
   """mcba_undistort_maps: [C, H, W, 2] float32, the source coordinate (x, y) of every pixel of the undistorted image of
-  image_size = (width, height); P = None: each camera's own matrix (cv2.initUndistortRectifyMap(K, dist, R, P, size, CV_32FC2))."""
+  image_size = (width, height); P = None: each camera's own matrix (cv2.initUndistortRectifyMap(K, dist, R, P, size, CV_32FC2)).
+  correction: mcba_undistort_maps_corrected, the maps of the corrected cameras."""
   inp = CameraSetInputs(cameras, R, P)
+  if correction is not None:
+    from . import correction as _correction
+    return _correction.undistort_maps(inp, image_size, correction)
   w, h = int(image_size[0]), int(image_size[1])
   maps = np.empty((inp.n, h, w, 2), dtype=np.float32)
   s = inp.struct()
@@ -138,13 +150,17 @@ def remap(images, maps, map_of_image=None, border=0.0):
   return batch.shaped(out)
 
 
-def undistort_images(cameras, images, camera_of_image=None, image_size=None, R=None, P=None, border=0.0):
+def undistort_images(cameras, images, camera_of_image=None, image_size=None, R=None, P=None, border=0.0, correction=None):
   """mcba_undistort_images: remap(images, undistort_maps(cameras, image_size, R, P), camera_of_image) in one launch and without
-  the maps; image_size = (width, height) of the result, None: that of the images."""
+  the maps; image_size = (width, height) of the result, None: that of the images.  correction: mcba_undistort_images_corrected,
+  the remap through the corrected maps, which stay on the device."""
   batch = ImageBatch(images)
   inp = CameraSetInputs(cameras, R, P)
   of = np.zeros(batch.n, dtype=np.int32) if camera_of_image is None else inp.index(camera_of_image, batch.n)
   wd, hd = (batch.w, batch.h) if image_size is None else (int(image_size[0]), int(image_size[1]))
+  if correction is not None:
+    from . import correction as _correction
+    return _correction.undistort_images(inp, batch, of, hd, wd, border, correction)
   out = batch.output(hd, wd)
   s = inp.struct()
   _entry("undistort_images")(C.byref(s), _dp(inp.R), _dp(inp.P), batch.data.ctypes.data_as(C.c_void_p), batch.n, batch.h, batch.w,
