@@ -825,6 +825,49 @@ int32_t mcba_rig_view_information(const mcba_camera_set* cams, const double* cam
  * rounds with their transfers (HIP events), [2] downloads, [3] the whole call; *n_slots (or NULL) = (view, camera) slots launched */
 int32_t mcba_debug_rig_view_information_ms(double* ms /*[4]*/, int64_t* n_slots);
 
+/* --- using a calibration: 3-D uncertainty of triangulated points ---------------------------------------------------- */
+/* The 3 x 3 covariance of the point a camera group triangulates, under the covariance of the calibration itself (cov_cal) and
+ * under the pixel noise of the point alone (cov_noise = sigma2 H^-1, what mcba_triangulate reports) (csrc/mcba_recon.h, DESIGN.md
+ * 3.20).  A job is a group of G = 2 .. MCBA_RECON_MAX_CAMERAS cameras of `cams` (slot s = cameras[s], no camera twice), a reference
+ * (< 0: the point is expressed in the rig frame; a camera of the group: in that camera's frame, the gauge-free form in which a common
+ * motion of all camera poses cancels), and per slot W [MCBA_RIG_COLUMNS, r] row-major in the columns of mcba_rig_camera.W: fx fy cx cy
+ * k0..k13 | left perturbation (omega, tau) of camera_poses[c]; one r = 0 .. MCBA_RIG_MAX_R for the job, the image size and
+ * `unconstrained` != 0: a parameter of the camera that no residual constrains and that is not held.  The job's n points follow those
+ * of the job before it in `points` [n_total, 3] (rig frame); masks [n_total] or NULL: bit s set = slot s may be used.
+ * Camera s is a VIEW of a point when the point lies in front of it, inside the monotone range of its model and projects into
+ * [-margin, W + margin) x [-margin, H + margin); the other cameras drop out for that point.  With J_c the 2 x 3 derivative of the
+ * pixel, P_c the 2 x 24 derivative by the columns of c and H = sum J_c^T J_c over the views: d X = -H^-1 sum_c J_c^T P_c W_c per
+ * column of the factor -- exact at the noise-free pixels of X; for a point triangulated from noisy pixels the Gauss-Newton
+ * approximation at the model-projected pixels.  cov_cal = sum over the columns of dX dX^T, positive semi-definite by construction;
+ * r = 0 returns exactly 0.  camera_poses [C, 3, 4] rig -> camera.
+ * Outputs: cov_cal, cov_noise [n_total, 6] upper triangles (xx xy xz yy yz zz), NaN unless OK; n_views [n_total]; views [n_total]
+ * the mask of the slots that are views; status [n_total] MCBA_RECON_*.  Refused, with nothing launched: G outside 2 .. 8, r above
+ * MCBA_RIG_MAX_R, a reference that is no camera of the group, a camera twice in a group, points that are not finite, an
+ * unsupported camera family.  Zero points launch nothing.  Handle-less like mcba_projection_uncertainty; same error convention,
+ * the caller owns every array.                                                                                                  */
+#define MCBA_RECON_MAX_CAMERAS 8
+#define MCBA_RECON_OK 0
+#define MCBA_RECON_TOO_FEW 1        /* fewer than two views                                                                  */
+#define MCBA_RECON_DEGENERATE 2     /* a Cholesky pivot of H at or below 1e-12 trace(H): the rays do not fix a point          */
+#define MCBA_RECON_UNCONSTRAINED 3  /* a view, or the reference camera, is flagged unconstrained                              */
+typedef struct mcba_recon_job {
+  int32_t G;                                     /* cameras of the group */
+  int32_t cameras[MCBA_RECON_MAX_CAMERAS];       /* slot -> camera of `cams` */
+  int32_t reference;                             /* a camera of the group, or < 0: the rig frame */
+  int32_t r;                                     /* columns of every W */
+  const double* W[MCBA_RECON_MAX_CAMERAS];       /* [MCBA_RIG_COLUMNS, r] per slot */
+  uint8_t unconstrained[MCBA_RECON_MAX_CAMERAS];
+  double image_w[MCBA_RECON_MAX_CAMERAS], image_h[MCBA_RECON_MAX_CAMERAS];
+  int64_t n;                                     /* points of this job */
+} mcba_recon_job;
+int32_t mcba_reconstruction_uncertainty(const mcba_camera_set* cams, const double* camera_poses, int32_t n_jobs,
+                                        const mcba_recon_job* jobs, const double* points, const uint64_t* masks, double sigma2,
+                                        double margin, double* cov_cal, double* cov_noise, int32_t* n_views, uint64_t* views,
+                                        uint8_t* status);
+/* timing of the last mcba_reconstruction_uncertainty call of this thread, milliseconds: [0] uploads, [1] kernel (HIP events around
+ * the launch), [2] downloads, [3] the whole call; *n_points (or NULL) = points launched                                        */
+int32_t mcba_debug_reconstruction_uncertainty_ms(double* ms /*[4]*/, int64_t* n_points);
+
 /* --- residual field: the systematic part of the reprojection error ------------------------ */
 /* Gram matrices of a smooth vector field fitted to the residuals as a function of the OBSERVED pixel.  Not part of the reference.
  *   - model: per camera a tensor-product uniform cubic B-spline field e(u, v) in R^2 over [0, W] x [0, H] with nx x ny intervals:

@@ -143,6 +143,11 @@ class RigCamera(C.Structure):   # mcba_rig_camera
   _fields_ = [("unconstrained", C.c_int32), ("reserved", C.c_int32), ("W", c_double_p), ("image_w", C.c_double), ("image_h", C.c_double)]
 
 
+class ReconJob(C.Structure):   # mcba_recon_job
+  _fields_ = [("G", C.c_int32), ("cameras", C.c_int32 * 8), ("reference", C.c_int32), ("r", C.c_int32), ("W", c_double_p * 8),
+              ("unconstrained", C.c_uint8 * 8), ("image_w", C.c_double * 8), ("image_h", C.c_double * 8), ("n", C.c_int64)]
+
+
 class RigView(C.Structure):   # mcba_rig_view
   _fields_ = [("board", C.c_int32), ("min_points", C.c_int32), ("pose", C.c_double * 12)]
 
@@ -167,6 +172,8 @@ GUIDE_OK, GUIDE_TOO_FEW, GUIDE_DEGENERATE, GUIDE_UNCONSTRAINED = 0, 1, 2, 3   # 
 GUIDE_BY_FOCUS, GUIDE_BY_GAIN = 0, 1                  # MCBA_GUIDE_BY_*
 GUIDE_MAX_R = 18                                      # MCBA_GUIDE_MAX_R
 RIG_MAX_R, RIG_COLUMNS = 128, 24                      # MCBA_RIG_MAX_R, MCBA_RIG_COLUMNS
+RECON_OK, RECON_TOO_FEW, RECON_DEGENERATE, RECON_UNCONSTRAINED = 0, 1, 2, 3   # MCBA_RECON_*
+RECON_MAX_CAMERAS = 8                                 # MCBA_RECON_MAX_CAMERAS
 PIXEL_U8, PIXEL_F32 = 0, 1                            # MCBA_PIXEL_*
 UNDISTORT_OK, UNDISTORT_NOT_CONVERGED = 0, 1          # MCBA_UNDISTORT_*
 
@@ -237,6 +244,10 @@ SYMBOLS = [
                                             C.c_double, C.c_double, C.POINTER(RigFocus), C.c_int32, C.c_int32, C.c_int32,
                                             C.POINTER(RigResult)]),
   ("mcba_debug_rig_view_information_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_reconstruction_uncertainty", C.c_int32, [C.POINTER(CameraSet), c_double_p, C.c_int32, C.POINTER(ReconJob), c_double_p,
+                                                  C.POINTER(C.c_uint64), C.c_double, C.c_double, c_double_p, c_double_p, c_int32_p,
+                                                  C.POINTER(C.c_uint64), c_uint8_p]),
+  ("mcba_debug_reconstruction_uncertainty_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_error_stats", C.c_int32, [H, c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), c_double_p,
                                    C.POINTER(C.c_int64), c_double_p]),
   ("mcba_error_count", C.c_int32, [H, C.c_int32, C.POINTER(C.c_int64)]),

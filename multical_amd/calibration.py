@@ -759,11 +759,15 @@ class Calibration(parameters.Parameters):
       return np.asarray(m.pose_start), np.asarray(m.pose_end)
     return np.asarray(m.frame_poses.poses), None
 
-  def triangulate(self, inliers_only=True, sigma=None, max_iterations=20):
+  def triangulate(self, inliers_only=True, sigma=None, max_iterations=20, calibration_cov=False, hold=None):
     """Every corner of the point table intersected from the cameras that saw it in its frame (multical_amd.triangulate, one launch,
     M = B * P): Table(points [F, B, P, 3], valid [F, B, P], n_views, cov [F, B, P, 3, 3], status, error [C, F, B, P]) in the frame
     of `world_points`.  The mask is `inliers` (inliers_only) or `valid`; a corner is valid where the triangulation converged, which
-    takes two cameras at least."""
+    takes two cameras at least.  `cov` is the pixel noise of the corner alone; calibration_cov=True adds cov_cal [F, B, P, 3, 3], the
+    covariance of the same corner under `covariance(hold)` of the intrinsics and camera poses (multical_amd.reconstruction, one more
+    launch over the valid corners, the views offered to each corner, in the frame of `cov`; NaN where the corner is not valid or its
+    calibration part is not defined).  For corners with non-zero residuals cov_cal is the Gauss-Newton approximation at the
+    model-projected pixels; it is common to all corners and does not average out."""
     from . import triangulate as tri
     C, F, B, P = self.point_table.valid.shape
     mask = self.inliers if inliers_only else self.valid
@@ -772,9 +776,29 @@ class Calibration(parameters.Parameters):
     r = tri.triangulate_rig(self.cameras, self.camera_poses.poses, start, np.asarray(self.point_table.points).reshape(C, F, B * P, 2),
                             np.asarray(mask).reshape(C, F, B * P), rig_poses_end=end, view_valid=view_valid, sigma=sigma,
                             max_iterations=max_iterations)
-    return Table.create(points=r.points.reshape(F, B, P, 3), valid=(r.status == tri.OK).reshape(F, B, P),
-                        n_views=r.n_views.reshape(F, B, P), cov=r.cov.reshape(F, B, P, 3, 3), status=r.status.reshape(F, B, P),
-                        error=r.error.reshape(C, F, B, P))
+    out = Table.create(points=r.points.reshape(F, B, P, 3), valid=(r.status == tri.OK).reshape(F, B, P),
+                       n_views=r.n_views.reshape(F, B, P), cov=r.cov.reshape(F, B, P, 3, 3), status=r.status.reshape(F, B, P),
+                       error=r.error.reshape(C, F, B, P))
+    if not calibration_cov:
+      return out
+    offered = np.asarray(mask).reshape(C, F, B, P) & view_valid[:, :, None, None]
+    return Table(out._extend(cov_cal=self._triangulated_cov_cal(out.points, out.valid, offered, start, hold)))
+
+  def _triangulated_cov_cal(self, points, valid, offered, rig_poses, hold):
+    """cov_cal [F, B, P, 3, 3] of the world points [F, B, P, 3] that are `valid`, seen through the cameras offered [C, F, B, P] in
+    frames at rig_poses [F, 4, 4]: one job of all cameras over the valid corners in the rig frame of their frame, turned back"""
+    from . import reconstruction
+    C = offered.shape[0]
+    if C > reconstruction.MAX_CAMERAS:
+      raise ValueError(f"triangulate(calibration_cov=True): {C} cameras; a group has at most {reconstruction.MAX_CAMERAS}")
+    f, b, p = np.nonzero(valid)
+    R, t = np.asarray(rig_poses)[f, :3, :3], np.asarray(rig_poses)[f, :3, 3]
+    X = np.einsum("nij,nj->ni", R, points[f, b, p]) + t
+    masks = (offered[:, f, b, p].astype(np.uint64) << np.arange(C, dtype=np.uint64)[:, None]).sum(axis=0).astype(np.uint64)
+    u = self._reconstruction_uncertainty(self.covariance(hold=hold), None, None, X, masks, margin=1e9)
+    cal = np.full(valid.shape + (3, 3), np.nan)
+    cal[f, b, p] = np.einsum("nji,njk,nkl->nil", R, u.cov_cal, R)
+    return cal
 
   def reconstruction_error(self, inliers_only=True):
     """How good the calibration is in the units of the boards: the distance of every triangulated corner from where the rig chain
@@ -923,6 +947,91 @@ class Calibration(parameters.Parameters):
            f"max={float(std[worst]):.4f} px at ({at[0]:.0f}, {at[1]:.0f}), {100.0 * float((std[ok] < sigma).mean()):.0f}% of cells "
            f"below sigma={sigma:.3f} px")
     return u
+
+  # --- 3-D uncertainty of triangulated points -----------------------------------------------------
+  def _median_board_distance(self, a):
+    """median distance of the board centres from camera a over the views of the point table in which a saw the board"""
+    start, _ = self._rig_poses()
+    seen = np.asarray(self.point_table.valid)[a].any(axis=-1) & np.asarray(self.motion.valid)[:, None] & \
+        np.asarray(self.board_poses.valid)[None, :]
+    f, b = np.nonzero(seen)
+    if len(f) == 0:
+      return float("nan")
+    centres = np.array([np.asarray(bd.adjusted_points, dtype=np.float64).reshape(-1, 3).mean(axis=0) for bd in self.boards])
+    T = np.asarray(self.camera_poses.poses)[a][None] @ np.asarray(start)[f] @ np.asarray(self.board_poses.poses)[b]
+    at = np.einsum("nij,nj->ni", T[:, :3, :3], centres[b]) + T[:, :3, 3]
+    return float(np.median(np.linalg.norm(at, axis=1)))
+
+  def _reconstruction_uncertainty(self, cov, cameras, reference, points, masks=None, pixels=None, grid=(16, 12), distances=None,
+                                  margin=0.0):
+    from . import reconstruction
+    camera_index, pose_index = self._shared_layout()
+    rtvecs = np.asarray(self.camera_poses.params, dtype=np.float64).reshape(-1, 6)
+    out = reconstruction.reconstruction_uncertainty(list(self.cameras), np.asarray(self.camera_poses.poses), cov, camera_index, pose_index,
+                                                    group=cameras, reference=reference, points=points, pixels=pixels, grid=grid,
+                                                    distances=distances, masks=masks, margin=margin, rtvecs=rtvecs)
+    return out._extend(sigma2=cov.sigma2, dof=cov.dof)
+
+  def reconstruction_uncertainty(self, cameras=None, reference=None, distances=None, grid=(16, 12), points=None, hold=None,
+                                 sigma2=None):
+    """How well the rig measures 3-D: the 3 x 3 covariance of the point that the group `cameras` (2 .. 8 indices; None: all)
+    triangulates, under `covariance(hold, sigma2)` of the intrinsics and camera poses (cov_cal: systematic, the same for every point
+    of a scene, growing with the square of the distance) beside the pixel noise of the point alone (cov_noise, what triangulate()
+    reports) (multical_amd.reconstruction, one covariance and one device call).  reference=None: the point in the rig frame;
+    reference=a: in the frame of camera a of the group, the gauge-free form.  points [n, 3] in the rig frame, or the centres of
+    `grid` in the image of the reference camera (None: the first of the group) at every one of `distances` from it (None: 0.5, 1, 2,
+    4, 8 x the median distance of the boards it saw).  A camera is a view of a point where the point projects into its image.
+    Returns struct(cov_cal, cov_noise, cov_total [.., 3, 3], n_views, views, status (reconstruction.OK / TOO_FEW / DEGENERATE /
+    UNCONSTRAINED; NaN where not OK), points, range_std_cal, lateral_std_cal, range_std_noise, lateral_std_noise (along / across the
+    line from the reference origin), r, distances, sigma2, dof); leading shape [n] or [D, gh, gw].  Exact for the point triangulated
+    from its noise-free pixels; the Gauss-Newton approximation at the model-projected pixels for a point with residuals.  The motion
+    model plays no part; correlations between points are not returned (differences of nearby points are better than cov_cal says)."""
+    if self.optimize["boards"] is True:
+      raise ValueError("reconstruction_uncertainty: not supported with the boards block optimised (the board points would join the "
+                       "shared system, as for projection_uncertainty)")
+    if points is None and distances is None:
+      members = list(range(self.size.cameras)) if cameras is None else [int(c) for c in np.atleast_1d(cameras)]
+      a = members[0] if reference is None else int(reference)
+      distances = np.array([0.5, 1.0, 2.0, 4.0, 8.0]) * self._median_board_distance(a)
+    u = self._reconstruction_uncertainty(self.covariance(hold=hold, sigma2=sigma2), cameras, reference, points, grid=grid,
+                                         distances=distances)
+    return u._extend(distances=None if distances is None else np.asarray(distances, dtype=np.float64))
+
+  def report_reconstruction_uncertainty(self, stage="", reference=None):
+    """One line per camera pair (reference, b) through the "calibration" logger: at 0.5, 1, 2, 4 and 8 x the median distance of the
+    boards the reference camera saw, on the ray of its image centre, the range error of the pair's triangulated point from the
+    calibration / from the pixel noise of one point, in millimetres (boards in metres), and the distance at which the calibration's
+    part overtakes the noise (interpolated between the five on a logarithmic scale)."""
+    if self.optimize["boards"] is True:
+      raise ValueError("report_reconstruction_uncertainty: not supported with the boards block optimised")
+    from . import reconstruction
+    a = 0 if reference is None else int(reference)
+    cov = self.covariance()
+    names = getattr(self.camera_poses, "names", None) or [f"cam{i}" for i in range(self.size.cameras)]
+    w, h = self.cameras[a].image_size
+    d = np.array([0.5, 1.0, 2.0, 4.0, 8.0]) * self._median_board_distance(a)
+    out = {}
+    for b in range(self.size.cameras):
+      if b == a:
+        continue
+      u = self._reconstruction_uncertainty(cov, [a, b], a, None, pixels=[[0.5 * (w - 1), 0.5 * (h - 1)]], distances=d)
+      out[b] = u
+      cal, noise, ok = u.range_std_cal[:, 0], u.range_std_noise[:, 0], u.status[:, 0] == reconstruction.OK
+      if not ok.any():
+        info(f"{stage} {names[a]}-{names[b]}: range uncertainty not defined (no distance is seen by both and constrained)")
+        continue
+      cells = " ".join(f"{1e3 * cal[i]:.3f}/{1e3 * noise[i]:.3f}@{d[i]:.2f}" if ok[i] else f"-@{d[i]:.2f}" for i in range(len(d)))
+      with np.errstate(invalid="ignore", divide="ignore"):
+        lr = np.where(ok, np.log(cal / noise), np.nan)
+      cross = f"calibration {'above' if np.nanmin(lr) > 0 else 'below'} the noise of one point at every distance"
+      for i in range(len(d) - 1):
+        if np.isfinite(lr[i]) and np.isfinite(lr[i + 1]) and (lr[i] <= 0) != (lr[i + 1] <= 0):
+          at = float(np.exp(np.log(d[i]) - lr[i] / (lr[i + 1] - lr[i]) * np.log(d[i + 1] / d[i])))
+          cross = (f"calibration overtakes the noise of one point at {at:.2f}" if lr[i] <= 0 else
+                   f"calibration above the noise of one point up to {at:.2f}")
+          break
+      info(f"{stage} {names[a]}-{names[b]}: range std calibration/noise mm@distance {cells}; {cross}")
+    return out
 
   # --- comparing two calibrations (DESIGN.md 3.15) -----------------------------------------------------------------
   def _other_rig(self, other):
