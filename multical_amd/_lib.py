@@ -295,6 +295,7 @@ SYMBOLS = [
   ("mcba_debug_gn_step", C.c_int32, [H, C.c_double, c_double_p, c_double_p, c_double_p]),
   ("mcba_debug_mfma_probe", C.c_int32, [c_double_p, c_double_p]),
   ("mcba_debug_chol", C.c_int32, [H, C.c_int32, c_double_p, c_double_p, C.c_double, C.c_int32, c_double_p]),
+  ("mcba_debug_set_error_table", C.c_int32, [H, c_double_p, c_double_p]),
   ("mcba_debug_linearize_profile", C.c_int32, [H, c_double_p, C.POINTER(C.c_longlong)]),
   ("mcba_debug_lsmr_products", C.c_int32, [H, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
   ("mcba_debug_lsmr_fused_products", C.c_int32, [H, c_double_p, c_double_p, c_double_p, c_double_p]),

@@ -421,6 +421,12 @@ class Handle(object):
                                    int(blocked), _ptr(out, C.c_double)))
     return out
 
+  def debug_set_error_table(self, x, table):
+    """tests: plant the [C,F,B,P] error table the outlier loop reads at x (mcba_debug_set_error_table)."""
+    x, table = self._x(x), _f64(table)
+    assert table.shape == tuple(self.shape), f"error table shape {table.shape} != {self.shape}"
+    check(self.lib.mcba_debug_set_error_table(self.h, _ptr(x, C.c_double), _ptr(table, C.c_double)))
+
   # --- outlier loop on the device ---------------------------------------------------------------------------------
   def error_stats(self, x, quantiles=(0, 0.25, 0.5, 0.75, 1), inliers_only=False):
     """error_stats(Calibration.reprojection_error) of the reference (calibration.py:304-310) computed on the device:

@@ -2011,6 +2011,37 @@ int32_t mcba_debug_chol(mcba_handle h, int32_t ns, const double* S, const double
   API_END
 }
 
+// debug: plant the per-point error table the outlier loop reads (tests of the radix select / rejection on values geometry cannot
+// produce).  The true table is evaluated at x first, so the err_x cache names x and every later call at x finds the planted values;
+// a call at another x recomputes.  Nothing is written unless every valid slot's value is accepted.
+int32_t mcba_debug_set_error_table(mcba_handle h, const double* x, const double* err) {
+  API_BEGIN
+  REQUIRE(h && x && err, "null argument");
+  g_fill_stream = h->stream;
+  const Dims& d = h->d;
+  REQUIRE(!h->allreduce && d.shard_world == 0 && d.f0 == 0 && d.Fl == d.F,
+          "error table: a frame-sharded handle is not supported (use a plain handle)");
+  compute_errors(h, x);
+  const size_t ns = (size_t)d.slots();
+  std::vector<uint8_t> ev(ns);
+  std::vector<double> fm(ns);
+  HIP_OK(hipMemcpyAsync(ev.data(), h->evalid.p, ns, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipMemcpyAsync(fm.data(), h->err_fm.p, ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  sync(h);
+  const long long nref = (long long)d.C * d.F * d.B * d.P;
+  for (long long i = 0; i < nref; ++i) {
+    const long long s = d.ref_to_slot(i);
+    if (s < 0 || !ev[(size_t)s]) continue;       // (values at slots that are not valid are ignored)
+    REQUIRE(!std::isnan(err[i]), "error table: NaN at valid entry " + std::to_string(i));
+    REQUIRE(!std::signbit(err[i]), "error table: negative-signed value at valid entry " + std::to_string(i) +
+                                       " (the selection orders errors >= +0 by their bit pattern)");
+    fm[(size_t)s] = err[i];
+  }
+  HIP_OK(hipMemcpyAsync(h->err_fm.p, fm.data(), ns * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  sync(h);
+  API_END
+}
+
 // debug: one MFMA f64 16x16x4 with an asymmetric operand pair; out[16][16] = A^T B for V = [A | B] (4 x 32)
 int32_t mcba_debug_mfma_probe(const double* V, double* out) {
   API_BEGIN

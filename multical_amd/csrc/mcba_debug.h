@@ -33,6 +33,12 @@ int32_t mcba_debug_linearize_profile(mcba_handle h, const double* x, long long* 
 /* (S + reg I) p = rhs with the device Cholesky kernels; blocked != 0 forces the multi-workgroup path              */
 int32_t mcba_debug_chol(mcba_handle h, int32_t ns, const double* S, const double* rhs, double reg, int32_t blocked,
                         double* p_out);
+/* plant the per-point error table of the outlier loop: err[C,F,B,P] (the layout mcba_reprojection_error returns) replaces the
+ * handle's frame-major errors and x is recorded as the point they were evaluated at, so that mcba_error_stats,
+ * mcba_reject_outliers and mcba_adjust_outliers(num_adjustments = 0) AT THE SAME x work on the planted values; a call at any
+ * other x recomputes the true table.  Values at slots that are not valid are ignored.  Refused: a frame-sharded handle, and a
+ * valid-slot value that is NaN or has the sign bit set (-0.0 included: the radix select orders errors >= +0 by bit pattern) */
+int32_t mcba_debug_set_error_table(mcba_handle h, const double* x, const double* err);
 /* one v_mfma_f64_16x16x4_f64 on V = [A | B] (4 x 32, row-major): out[16][16] = A^T B (operand-layout self-test)     */
 int32_t mcba_debug_mfma_probe(const double* V, double* out);
 
