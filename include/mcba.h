@@ -868,6 +868,35 @@ int32_t mcba_reconstruction_uncertainty(const mcba_camera_set* cams, const doubl
  * the launch), [2] downloads, [3] the whole call; *n_points (or NULL) = points launched                                        */
 int32_t mcba_debug_reconstruction_uncertainty_ms(double* ms /*[4]*/, int64_t* n_points);
 
+/* --- using a calibration: uncertainty of measured lengths (covariance between triangulated points) --------------------- */
+/* The covariance of the DIFFERENCE of two triangulated points and of the length between them (csrc/mcba_recon.h).
+ * The calibration's error is common to all points of a scene: it moves both ends of a short bar by nearly the same vector, so the
+ * error of a length is far below sqrt(var_a + var_b) of the per-point cov_cal.  The arguments of mcba_reconstruction_uncertainty,
+ * and per job n_pairs[j] pairs (a, b) of indices into the job's own points: pairs [n_pairs_total, 2], those of a job after those of
+ * the job before it.  With z_j(X) the response of mcba_reconstruction_uncertainty to column j of the factor:
+ *   cov_diff_cal   [K, 6]  sum_j d_j d_j^T, d_j = z_j(X_a) - z_j(X_b): subtracted per column before squaring, positive semi-definite
+ *                          by construction (never formed as C_a + C_b - C_ab - C_ab^T); exactly 0 for a == b and for r = 0
+ *   cross_cal      [K, 9]  sum_j z_j(X_a) z_j(X_b)^T, row-major 3 x 3: cross(b, a) = cross(a, b)^T, cross(a, a) = cov_cal of a; from
+ *                          these and cov_cal a caller assembles the joint covariance of a small set of points
+ *   cov_diff_noise [K, 6]  sigma2 (H_a^-1 + H_b^-1) (the pixel noise of two points is independent); exactly 0 for a == b
+ *   length         [K]     |X_a - X_b|
+ *   length_var_cal, length_var_noise [K]  u^T cov_diff_* u, u the unit vector between the points; NaN where length == 0.  To first
+ *                          order they do not depend on the reference or the rig frame (a common motion of the output frame moves
+ *                          both ends rigidly, and its rotation term is perpendicular to u)
+ *   views_a, views_b [K]   the view masks of the two ends (each end keeps its own views, masks and margin as for a single point)
+ *   status         [K]     MCBA_RECON_*: that of a unless it is OK, then that of b.  Unless OK every output is NaN except length and
+ *                          the view masks.
+ * Any output pointer may be NULL.  Refused, with nothing launched: what mcba_reconstruction_uncertainty refuses, a negative
+ * n_pairs[j], an index of `pairs` outside [0, n) of its job.  Zero pairs launch nothing.                                          */
+int32_t mcba_reconstruction_pairs(const mcba_camera_set* cams, const double* camera_poses, int32_t n_jobs, const mcba_recon_job* jobs,
+                                  const double* points, const uint64_t* masks, const int64_t* n_pairs, const int64_t* pairs,
+                                  double sigma2, double margin, double* cov_diff_cal, double* cross_cal, double* cov_diff_noise,
+                                  double* length, double* length_var_cal, double* length_var_noise, uint64_t* views_a,
+                                  uint64_t* views_b, uint8_t* status);
+/* timing of the last mcba_reconstruction_pairs call of this thread, milliseconds: [0] uploads, [1] kernel (HIP events around the
+ * launch), [2] downloads, [3] the whole call; *n_pairs (or NULL) = pairs launched                                                */
+int32_t mcba_debug_reconstruction_pairs_ms(double* ms /*[4]*/, int64_t* n_pairs);
+
 /* --- residual field: the systematic part of the reprojection error ------------------------ */
 /* Gram matrices of a smooth vector field fitted to the residuals as a function of the OBSERVED pixel.  Not part of the reference.
  *   - model: per camera a tensor-product uniform cubic B-spline field e(u, v) in R^2 over [0, W] x [0, H] with nx x ny intervals:

@@ -248,6 +248,11 @@ SYMBOLS = [
                                                   C.POINTER(C.c_uint64), C.c_double, C.c_double, c_double_p, c_double_p, c_int32_p,
                                                   C.POINTER(C.c_uint64), c_uint8_p]),
   ("mcba_debug_reconstruction_uncertainty_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_reconstruction_pairs", C.c_int32, [C.POINTER(CameraSet), c_double_p, C.c_int32, C.POINTER(ReconJob), c_double_p,
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_double, C.c_double,
+                                            c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), c_uint8_p]),
+  ("mcba_debug_reconstruction_pairs_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_error_stats", C.c_int32, [H, c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), c_double_p,
                                    C.POINTER(C.c_int64), c_double_p]),
   ("mcba_error_count", C.c_int32, [H, C.c_int32, C.POINTER(C.c_int64)]),

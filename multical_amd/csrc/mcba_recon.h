@@ -18,7 +18,9 @@
 //   cov_noise = sigma2 H^-1        R_a (sigma2 H^-1) R_a^T with a reference camera
 // Status: fewer than two views TOO_FEW; a Cholesky pivot of H at or below 1e-12 trace(H) DEGENERATE (the rule of mcba_triangulate.h);
 // a view or the reference camera whose factor is flagged unconstrained UNCONSTRAINED; decided in this order.  Anything but OK: NaN.
-// MCBA_HD like mcba_uncertainty.h: k_reconstruction_uncertainty (mcba_recon_kernels.h) and tests/recon_host compile this source.
+// Pairs of points of a job -- the covariance of X_a - X_b, of the length |X_a - X_b| and cov(X_a, X_b) -- follow below (pair_query).
+// MCBA_HD like mcba_uncertainty.h: k_reconstruction_uncertainty, k_reconstruction_pairs (mcba_recon_kernels.h), tests/recon_host and
+// tests/length_host compile this source.
 #pragma once
 #include <stdint.h>
 #include "mcba_triangulate.h"
@@ -240,6 +242,109 @@ MCBA_HD void query(const double* rec, const double* Wj, const double* X, uint64_
     for (int l = 1; l < LANES; ++l) s += part[l][i];
     out.cov_cal[i] = s;
   }
+}
+
+// ---- pairs of points of one job: the covariance of X_a - X_b and of |X_a - X_b| ------------------------
+// The calibration's error is common to all points, so per column j of the factor the two ends move by nearly the same vector:
+//   d_j = z_j(X_a) - z_j(X_b)                the subtraction per column, BEFORE squaring -- never C_a + C_b - C_ab - C_ab^T
+//   cov_diff_cal = sum_j d_j d_j^T           positive semi-definite by construction; a == b: exactly 0
+//   cross_cal    = sum_j z_j(X_a) z_j(X_b)^T the full 3 x 3, row-major; cross(b, a) = cross(a, b)^T; a == b: the point's cov_cal
+// both in the LANES interleaved partial sums of cov_cal, added in the same order; r = 0: exactly 0.
+//   cov_diff_noise = cov_noise(a) + cov_noise(b)   (the pixel noise of two different points is independent); a == b: exactly 0
+//   length = |X_a - X_b|,  u = (X_a - X_b) / length taken to the output frame,  length_var_* = u^T cov_diff_* u; length == 0: NaN.
+// A common motion of the output frame moves both ends rigidly and its rotation term omega x (X_a - X_b) is perpendicular to u: to
+// first order length_var_* does not depend on the reference, the rig frame or any camera pose being held.
+// Each end keeps its own views (mask, margin).  Status: that of a unless it is OK, then that of b; anything but OK: NaN, the length
+// and the view masks of both ends excepted.
+struct PairResult {
+  double cov_diff_cal[6], cross_cal[9], cov_diff_noise[6], length, length_var_cal, length_var_noise;
+  int status;
+  uint64_t views_a, views_b;
+};
+MCBA_HD int pair_status(int status_a, int status_b) { return status_a != ST_OK ? status_a : status_b; }
+// d = za - zb into the pair's sums: diff [6] += d d^T, cross [9] += za zb^T
+MCBA_HD void add_pair(const double* za, const double* zb, double* diff, double* cross) {
+  const double d[3] = {za[0] - zb[0], za[1] - zb[1], za[2] - zb[2]};
+  add_outer(d, diff);
+  MCBA_UNROLL
+  for (int i = 0; i < 3; ++i) {
+    MCBA_UNROLL
+    for (int k = 0; k < 3; ++k) cross[3 * i + k] += za[i] * zb[k];
+  }
+}
+// what follows the sums: the noise of the difference, the length and the variances of the length; NaN where the pair is not OK
+MCBA_HD void pair_finish(const double* rec, const double* Xa, const double* Xb, bool same, int status_a, int status_b,
+                         const double* noise_a, const double* noise_b, const double* diff, const double* cross, PairResult& out) {
+  const double nan = undistort::quiet_nan();
+  out.status = pair_status(status_a, status_b);
+  const double dX[3] = {Xa[0] - Xb[0], Xa[1] - Xb[1], Xa[2] - Xb[2]};
+  out.length = sqrt(dX[0] * dX[0] + dX[1] * dX[1] + dX[2] * dX[2]);
+  const bool ok = out.status == ST_OK;
+  MCBA_UNROLL
+  for (int i = 0; i < 6; ++i) {
+    out.cov_diff_cal[i] = ok ? diff[i] : nan;
+    out.cov_diff_noise[i] = !ok ? nan : same ? 0.0 : noise_a[i] + noise_b[i];
+  }
+  MCBA_UNROLL
+  for (int i = 0; i < 9; ++i) out.cross_cal[i] = ok ? cross[i] : nan;
+  out.length_var_cal = out.length_var_noise = nan;
+  if (!ok || !(out.length > 0.0)) return;
+  double u[3] = {dX[0] / out.length, dX[1] / out.length, dX[2] / out.length};
+  const int ref = (int)rec[JR_REF];
+  if (ref >= 0) {                    // the covariances are in the frame of the reference camera
+    const double* T = slot_of(rec, ref) + SL_POSE;
+    const double v[3] = {u[0], u[1], u[2]};
+    MCBA_UNROLL
+    for (int i = 0; i < 3; ++i) u[i] = T[4 * i] * v[0] + T[4 * i + 1] * v[1] + T[4 * i + 2] * v[2];
+  }
+  double cu[3];
+  sym3_times(out.cov_diff_cal, u, cu);
+  out.length_var_cal = u[0] * cu[0] + u[1] * cu[1] + u[2] * cu[2];
+  sym3_times(out.cov_diff_noise, u, cu);
+  out.length_var_noise = u[0] * cu[0] + u[1] * cu[1] + u[2] * cu[2];
+}
+
+// one pair, plain loops in the orders stated above; same: a and b are one index
+MCBA_HD void pair_query(const double* rec, const double* Wj, const double* Xa, const double* Xb, uint64_t mask_a, uint64_t mask_b,
+                        bool same, double sigma2, PairResult& out) {
+  const int G = (int)rec[JR_G], r = (int)rec[JR_R], ldw = (int)rec[JR_LDW], ref = (int)rec[JR_REF];
+  double Ba[3 * KC * MAX_G], Bb[3 * KC * MAX_G];
+  Point pa, pb;
+  point_views(rec, Xa, mask_a, Ba, pa);
+  point_views(rec, Xb, mask_b, Bb, pb);
+  out.views_a = pa.views; out.views_b = pb.views;
+  double na[6] = {0, 0, 0, 0, 0, 0}, nb[6] = {0, 0, 0, 0, 0, 0};
+  double diff[LANES][6], cross[LANES][9], sd[6], sc[9];
+  for (int l = 0; l < LANES; ++l) {
+    for (int i = 0; i < 6; ++i) diff[l][i] = 0.0;
+    for (int i = 0; i < 9; ++i) cross[l][i] = 0.0;
+  }
+  if (pair_status(pa.status, pb.status) == ST_OK) {
+    noise_covariance(rec, pa, sigma2, na);
+    noise_covariance(rec, pb, sigma2, nb);
+    for (int j = 0; j < r; ++j) {
+      double ua[3] = {0.0, 0.0, 0.0}, ub[3] = {0.0, 0.0, 0.0}, pose[6] = {0, 0, 0, 0, 0, 0}, za[3], zb[3];
+      for (int k = 0; k < KC * G; ++k) {
+        const double w = Wj[(size_t)k * ldw + j];
+        ua[0] += Ba[k] * w; ua[1] += Ba[KC * G + k] * w; ua[2] += Ba[2 * KC * G + k] * w;
+        ub[0] += Bb[k] * w; ub[1] += Bb[KC * G + k] * w; ub[2] += Bb[2 * KC * G + k] * w;
+      }
+      if (ref >= 0)
+        for (int m = 0; m < 6; ++m) pose[m] = Wj[(size_t)(KC * ref + KI + m) * ldw + j];
+      response(rec, pa, ua, pose, za);
+      response(rec, pb, ub, pose, zb);
+      add_pair(za, zb, diff[j % LANES], cross[j % LANES]);
+    }
+  }
+  for (int i = 0; i < 6; ++i) {
+    sd[i] = diff[0][i];
+    for (int l = 1; l < LANES; ++l) sd[i] += diff[l][i];
+  }
+  for (int i = 0; i < 9; ++i) {
+    sc[i] = cross[0][i];
+    for (int l = 1; l < LANES; ++l) sc[i] += cross[l][i];
+  }
+  pair_finish(rec, Xa, Xb, same, pa.status, pb.status, na, nb, sd, sc, out);
 }
 
 // tests: G = -H^-1 [B_1 .. B_G] [3][KC G] with the reference term included (the unit columns of every parameter); the status

@@ -1,7 +1,8 @@
 // mcba_recon_driver.h -- host side of mcba_reconstruction_uncertainty that does not touch the device: argument checks and refusals,
 // the job records of mcba_recon.h, the jobs' factors [24 G][ldw] zero-padded and one after the other, and where each job's points
-// and tiles start.  Shared by the driver (mcba_recon.hip) and the host build of the mathematics (tests/recon_host), so that both
-// refuse the same calls with the same messages.
+// and tiles start; for mcba_reconstruction_pairs the same jobs and where each job's pairs and pair tiles start (plan_pairs).  Shared by
+// the driver (mcba_recon.hip) and the host builds of the mathematics (tests/recon_host, tests/length_host), so that both refuse the
+// same calls with the same messages.
 #pragma once
 #include <stdio.h>
 #include <string>
@@ -32,10 +33,10 @@ struct Plan {
 
 inline bool finite_arg(double v) { return v - v == 0.0; }
 
-inline bool plan_jobs(const mcba_camera_set* cams, const double* camera_poses, int32_t n_jobs, const mcba_recon_job* jobs,
-                      const double* points, double sigma2, double margin, const double* cov_cal, const double* cov_noise,
-                      const int32_t* n_views, const uint64_t* views, const uint8_t* status, Plan& out, std::string& err) {
-  const char* who = "mcba_reconstruction_uncertainty";
+// the jobs of either entry (`who` names it in the messages); outputs_there: no output the entry requires is null
+inline bool plan_jobs_of(const char* who, const mcba_camera_set* cams, const double* camera_poses, int32_t n_jobs,
+                         const mcba_recon_job* jobs, const double* points, double sigma2, double margin, bool outputs_there, Plan& out,
+                         std::string& err) {
   const std::string w(who);
   undistort::CameraPlan plan;
   if (!undistort::plan_cameras(cams, who, plan, err)) return false;
@@ -126,13 +127,61 @@ inline bool plan_jobs(const mcba_camera_set* cams, const double* camera_poses, i
     if (job.n > 0 && G > out.max_group) out.max_group = G;
   }
   out.n_points = out.first[n_jobs];
-  if (out.n_points > 0 && (!points || !cov_cal || !cov_noise || !n_views || !views || !status)) { err = w + ": null argument"; return false; }
+  if (out.n_points > 0 && (!points || !outputs_there)) { err = w + ": null argument"; return false; }
   for (int64_t i = 0; i < 3 * out.n_points; ++i)
     if (!finite_arg(points[i])) {
       snprintf(msg, sizeof msg, "%s: points: point %lld is not finite", who, (long long)(i / 3));
       err = msg;
       return false;
     }
+  return true;
+}
+
+inline bool plan_jobs(const mcba_camera_set* cams, const double* camera_poses, int32_t n_jobs, const mcba_recon_job* jobs,
+                      const double* points, double sigma2, double margin, const double* cov_cal, const double* cov_noise,
+                      const int32_t* n_views, const uint64_t* views, const uint8_t* status, Plan& out, std::string& err) {
+  return plan_jobs_of("mcba_reconstruction_uncertainty", cams, camera_poses, n_jobs, jobs, points, sigma2, margin,
+                      cov_cal && cov_noise && n_views && views && status, out, err);
+}
+
+// ---- mcba_reconstruction_pairs: the jobs as above (every output may be left out) and where each job's pairs and pair tiles start
+constexpr int PAIR_TILE = 8;      // pairs a wavefront serves at a time: the a ends in rows 0 .. 7 of the tile, the b ends in 8 .. 15
+constexpr const char* PAIRS_ENTRY = "mcba_reconstruction_pairs";
+
+struct PairPlan {
+  Plan jobs;                        // (its tile_first counts point tiles and is not used)
+  std::vector<int64_t> pair_first;  // [n_jobs + 1] first pair of every job
+  std::vector<int64_t> tile_first;  // [n_jobs + 1] first pair tile of every job
+  int64_t n_pairs = 0;
+  int max_group = 0;                // the widest group among the jobs that have a pair
+};
+
+inline bool plan_pairs(const mcba_camera_set* cams, const double* camera_poses, int32_t n_jobs, const mcba_recon_job* jobs,
+                       const double* points, const int64_t* n_pairs, const int64_t* pairs, double sigma2, double margin, PairPlan& out,
+                       std::string& err) {
+  const std::string w(PAIRS_ENTRY);
+  if (!plan_jobs_of(PAIRS_ENTRY, cams, camera_poses, n_jobs, jobs, points, sigma2, margin, true, out.jobs, err)) return false;
+  if (n_jobs > 0 && !n_pairs) { err = w + ": n_pairs is null"; return false; }
+  char msg[320];
+  out.pair_first.assign((size_t)n_jobs + 1, 0);
+  out.tile_first.assign((size_t)n_jobs + 1, 0);
+  out.max_group = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    if (n_pairs[j] < 0) { snprintf(msg, sizeof msg, "%s: job %d: n_pairs is negative", PAIRS_ENTRY, j); err = msg; return false; }
+    out.pair_first[j + 1] = out.pair_first[j] + n_pairs[j];
+    out.tile_first[j + 1] = out.tile_first[j] + (n_pairs[j] + PAIR_TILE - 1) / PAIR_TILE;
+    if (n_pairs[j] > 0 && jobs[j].G > out.max_group) out.max_group = jobs[j].G;
+  }
+  out.n_pairs = out.pair_first[n_jobs];
+  if (out.n_pairs > 0 && !pairs) { err = w + ": pairs is null"; return false; }
+  for (int j = 0; j < n_jobs; ++j)
+    for (int64_t k = 2 * out.pair_first[j]; k < 2 * out.pair_first[j + 1]; ++k)
+      if (pairs[k] < 0 || pairs[k] >= jobs[j].n) {
+        snprintf(msg, sizeof msg, "%s: pairs: pair %lld (%lld of job %d): index %lld is outside [0, n = %lld)", PAIRS_ENTRY,
+                 (long long)(k / 2), (long long)(k / 2 - out.pair_first[j]), j, (long long)pairs[k], (long long)jobs[j].n);
+        err = msg;
+        return false;
+      }
   return true;
 }
 
