@@ -313,6 +313,8 @@ SYMBOLS = [
   ("mcba_debug_set_lsmr_grid", C.c_int32, [H, C.c_int32]),
   ("mcba_debug_set_allreduce_trace", C.c_int32, [H, C.c_int32]),
   ("mcba_debug_set_lsmr_masks_form", C.c_int32, [H, C.c_int32]),
+  ("mcba_debug_set_grid_cap", C.c_int32, [C.c_int32]),
+  ("mcba_debug_last_capped_grid", C.c_int32, [C.POINTER(C.c_int32)]),
 ]
 
 _lib = None
@@ -347,6 +349,19 @@ def set_switch(name, value):
   rc = load().mcba_debug_set_switch(name.encode(), str(value).encode())
   if rc != 0:
     raise RuntimeError(load().mcba_last_error().decode("utf-8", "replace"))
+
+
+def set_grid_cap(cap):
+  """Upper bound on the grid of the handle-less families' grid-stride kernels (mcba_debug_set_grid_cap): tests only; process-wide,
+  effective from the next launch, 0 restores the built-in caps."""
+  check(load().mcba_debug_set_grid_cap(int(cap)))
+
+
+def last_capped_grid():
+  """grid.x of this thread's last launch of a capped grid-stride kernel (mcba_debug_last_capped_grid)."""
+  grid = C.c_int32(0)
+  check(load().mcba_debug_last_capped_grid(C.byref(grid)))
+  return int(grid.value)
 
 
 class McbaError(RuntimeError):

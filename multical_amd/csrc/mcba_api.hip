@@ -10,6 +10,7 @@
 //     Jacobian is computed exactly from the analytic normal equations (Schur elimination of the per-frame pose blocks
 //     + dense Cholesky of the reduced system), all on the GPU.  Only 2x2 algebra and control flow run on the host.
 #include <dlfcn.h>
+#include <atomic>
 #include <cmath>
 #include <limits>
 
@@ -36,6 +37,16 @@ __thread bool g_park_on_release = false;
 ResourceCache& resource_cache() {
   static ResourceCache* c = new ResourceCache();   // (never destroyed: the HIP runtime may be gone at exit)
   return *c;
+}
+namespace {
+std::atomic<int> g_grid_cap_override{0};   // mcba_debug_set_grid_cap; 0 = none
+__thread int g_last_capped_grid = 0;       // what capped_grid last returned on this thread
+}  // namespace
+int capped_grid(long long workgroups, long long builtin_cap) {
+  long long g = std::min(workgroups, builtin_cap);
+  const int over = g_grid_cap_override.load(std::memory_order_relaxed);
+  if (over > 0) g = std::min<long long>(g, over);
+  return g_last_capped_grid = (int)std::max<long long>(g, 1);
 }
 }  // namespace host
 }  // namespace mcba
@@ -2736,6 +2747,22 @@ int32_t mcba_debug_set_switch(const char* name, const char* value) {
   auto& t = dbg_switch_table();
   if (t.find(name) == t.end()) t[name] = value;
   else REQUIRE(t[name] == value, "a switch can be set once per process (most are latched on first use)");
+  API_END
+}
+
+/* test hooks (mcba_debug.h) of host::capped_grid: the process-wide override of the grid caps, and the grid of this thread's last
+ * capped launch.  Not latched: tests change the cap between calls of one process.                                           */
+int32_t mcba_debug_set_grid_cap(int32_t cap) {
+  API_BEGIN
+  REQUIRE(cap >= 0, "a grid cap is a positive number of workgroups, or 0 for the built-in caps");
+  g_grid_cap_override.store(cap, std::memory_order_relaxed);
+  API_END
+}
+
+int32_t mcba_debug_last_capped_grid(int32_t* grid) {
+  API_BEGIN
+  REQUIRE(grid, "null argument");
+  *grid = g_last_capped_grid;
   API_END
 }
 

@@ -85,6 +85,13 @@ int32_t mcba_debug_set_observation_covariance_route(mcba_handle h, int32_t sigma
  * [0] uploads, [1] kernel (HIP events around the launch), [2] downloads, [3] the whole call; *n_pixels (or NULL) = destination
  * pixels (points for the two point calls) the kernel wrote                                                                      */
 int32_t mcba_debug_undistort_ms(double* ms /*[4]*/, int64_t* n_pixels);
+/* process-wide upper bound on the grid of every kernel of the handle-less families that walks its work in a grid-stride loop
+ * (k_point_ops, k_undistort_map, k_remap_cubic, k_warp_points, k_triangulate, k_projection_uncertainty, k_projdiff_map,
+ * k_reconstruction_uncertainty, k_reconstruction_pairs): tests run the second and later rounds of those loops on small inputs.
+ * Takes effect at the next launch and may be changed between calls; 0 restores the built-in caps; negative: refused           */
+int32_t mcba_debug_set_grid_cap(int32_t cap);
+/* grid.x of this thread's last launch of one of those kernels (0 before the first)                                             */
+int32_t mcba_debug_last_capped_grid(int32_t* grid);
 
 #ifdef __cplusplus
 }

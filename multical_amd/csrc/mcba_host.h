@@ -68,6 +68,12 @@ inline void check_launch(const char* what) {
   if (e != hipSuccess) throw Error(std::string("kernel launch failed (") + what + "): " + hipGetErrorString(e));
 }
 
+// grid.x of a kernel that walks its workgroups' worth of work in a grid-stride loop: max(1, min(workgroups, builtin_cap, override)).
+// The override is process-wide (mcba_debug_set_grid_cap; 0 = none: the launch has the grid the built-in cap gives it) and lets a test
+// run the second and later rounds of such a loop on a small input.  The value returned is kept per thread for
+// mcba_debug_last_capped_grid.  Defined in mcba_api.hip.
+MCBA_PRIVATE int capped_grid(long long workgroups, long long builtin_cap);
+
 inline double now_seconds() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }

@@ -17,7 +17,7 @@ hipError_t fit_launch(const FitArgs& a, int n_fit_jobs, hipStream_t st) {
 
 void map_launch(const MapArgs& a, long long tiles, hipStream_t st) {
   if (tiles <= 0) return;
-  const int grid = (int)(tiles > PD_MAX_GRID ? PD_MAX_GRID : tiles);
+  const int grid = host::capped_grid(tiles, PD_MAX_GRID);
   hipLaunchKernelGGL(k_projdiff_map, dim3(grid), dim3(PD_THREADS), 0, st, a);
 }
 

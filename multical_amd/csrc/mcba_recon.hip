@@ -9,14 +9,14 @@ namespace recon {
 
 void recon_launch(const KernelArgs& a, long long tiles, int max_group, hipStream_t st) {
   if (tiles <= 0) return;
-  const int grid = (int)(tiles > RC_MAX_GRID ? RC_MAX_GRID : tiles);
+  const int grid = host::capped_grid(tiles, RC_MAX_GRID);
   if (max_group <= 4) hipLaunchKernelGGL(k_reconstruction_uncertainty<4>, dim3(grid), dim3(RC_THREADS), 0, st, a);
   else hipLaunchKernelGGL(k_reconstruction_uncertainty<8>, dim3(grid), dim3(RC_THREADS), 0, st, a);
 }
 
 void recon_pairs_launch(const PairKernelArgs& a, long long tiles, int max_group, hipStream_t st) {
   if (tiles <= 0) return;
-  const int grid = (int)(tiles > RC_MAX_GRID ? RC_MAX_GRID : tiles);
+  const int grid = host::capped_grid(tiles, RC_MAX_GRID);
   if (max_group <= 4) hipLaunchKernelGGL(k_reconstruction_pairs<4>, dim3(grid), dim3(RC_THREADS), 0, st, a);
   else hipLaunchKernelGGL(k_reconstruction_pairs<8>, dim3(grid), dim3(RC_THREADS), 0, st, a);
 }

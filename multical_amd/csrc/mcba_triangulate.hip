@@ -9,7 +9,7 @@ namespace triangulate {
 void triangulate_launch(const KernelArgs& a, hipStream_t st) {
   const long long rounds = (long long)a.t.F * ((a.M + TRI_THREADS - 1) / TRI_THREADS);
   if (rounds <= 0) return;
-  const int grid = (int)(rounds > TRI_MAX_GRID ? TRI_MAX_GRID : rounds);
+  const int grid = host::capped_grid(rounds, TRI_MAX_GRID);
   hipLaunchKernelGGL(k_triangulate, dim3(grid), dim3(TRI_THREADS), lds_bytes(a.t.C), st, a);
 }
 

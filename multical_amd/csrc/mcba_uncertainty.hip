@@ -8,7 +8,7 @@ namespace uncertainty {
 
 void uncertainty_launch(const KernelArgs& a, long long tiles, hipStream_t st) {
   if (tiles <= 0) return;
-  const int grid = (int)(tiles > UNC_MAX_GRID ? UNC_MAX_GRID : tiles);
+  const int grid = host::capped_grid(tiles, UNC_MAX_GRID);
   hipLaunchKernelGGL(k_projection_uncertainty, dim3(grid), dim3(UNC_THREADS), 0, st, a);
 }
 

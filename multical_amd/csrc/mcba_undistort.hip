@@ -11,7 +11,7 @@ namespace undistort {
 namespace {
 int grid_for(long long work_items, long long per_block) {
   const long long blocks = (work_items + per_block - 1) / per_block;
-  return (int)(blocks < 1 ? 1 : blocks > (1 << 20) ? (1 << 20) : blocks);
+  return host::capped_grid(blocks, 1 << 20);
 }
 
 template <int CH, class T, bool FUSED>

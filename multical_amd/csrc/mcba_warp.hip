@@ -11,8 +11,7 @@ namespace warp {
 void warp_points_launch(const WarpPointsArgs& a, hipStream_t st) {
   if (a.n <= 0) return;
   const long long blocks = (a.n + WARP_THREADS - 1) / WARP_THREADS;
-  hipLaunchKernelGGL(k_warp_points, dim3((int)(blocks > WARP_POINTS_MAX_BLOCKS ? WARP_POINTS_MAX_BLOCKS : blocks)), dim3(WARP_THREADS), 0,
-                     st, a);
+  hipLaunchKernelGGL(k_warp_points, dim3(host::capped_grid(blocks, WARP_POINTS_MAX_BLOCKS)), dim3(WARP_THREADS), 0, st, a);
 }
 
 void warp_map_launch(const WarpMapArgs& a, hipStream_t st) {

@@ -13,7 +13,9 @@ pytestmark = pytest.mark.gpu
 
 CAMERAS = uh.fixture_cameras()
 W, H = uh.IMAGE_SIZE
-SIZES = [(1, 1), (3, 2), (255, 3), (256, 4), (257, 5), (200, 150)]      # (width, height): flat path x 4, row path x 2
+# (width, height): flat path x 4, row path x 5 -- one x-tile of 256 columns (256, 200), two (260: one group in the second; 512: both
+# full) and three (516: one group in the third)
+SIZES = [(1, 1), (3, 2), (255, 3), (256, 4), (257, 5), (200, 150), (260, 4), (512, 3), (516, 5)]
 DTYPES = [np.uint8, np.float32]
 
 
@@ -97,18 +99,22 @@ def test_remap_identity_on_device():
 @pytest.mark.parametrize("channels", [1, 3])
 @pytest.mark.parametrize("dtype", DTYPES, ids=["u8", "f32"])
 def test_fused_equals_remap_through_device_maps(dtype, channels):
-  """undistort_images = remap(images, undistort_maps) byte for byte: every family, P = K and a zoomed-out P, a row-path and a
-  flat-path size; and the same call twice returns the same bytes"""
+  """undistort_images = remap(images, undistort_maps) byte for byte: every family, P = K and a zoomed-out P, two row-path sizes (one
+  and three x-tiles) and a flat-path size, every camera with an image and one camera without; and the same call twice returns the
+  same bytes"""
   n = len(CAMERAS) + 3
   of = (np.arange(n) * 5 % len(CAMERAS)).astype(np.int32)
+  gap = np.where(of == 2, 6, of).astype(np.int32)                   # camera 2 has no image, camera 6 has those as well
+  assert set(of) == set(range(len(CAMERAS))) and 2 not in gap and (gap == 6).sum() >= 2
   images = uh.noise_image(400 + channels, (n, H, W) + ((3,) if channels == 3 else ()), dtype)
-  for size in ((W, H), (57, 5)):
+  for size in ((W, H), (516, 5), (57, 5)):
     for kwargs in (dict(), dict(P=zoomed(CAMERAS))):
       maps = undistort.undistort_maps(CAMERAS, size, **kwargs)
-      two = undistort.remap(images, maps, of)
-      fused = undistort.undistort_images(CAMERAS, images, of, image_size=size, **kwargs)
-      assert fused.shape == two.shape and fused.tobytes() == two.tobytes()
-      assert undistort.undistort_images(CAMERAS, images, of, image_size=size, **kwargs).tobytes() == fused.tobytes()
+      for index in (of, gap):
+        two = undistort.remap(images, maps, index)
+        fused = undistort.undistort_images(CAMERAS, images, index, image_size=size, **kwargs)
+        assert fused.shape == two.shape and fused.tobytes() == two.tobytes()
+        assert undistort.undistort_images(CAMERAS, images, index, image_size=size, **kwargs).tobytes() == fused.tobytes()
   ms, count = undistort.last_call_ms()
   assert count == n * 57 * 5 and ms["kernel"] > 0.0
 
