@@ -973,6 +973,37 @@ int32_t mcba_undistort_images_corrected(const mcba_camera_set* cams, const mcba_
  * whole call; *n (or NULL) = points or pixels written                                                                   */
 int32_t mcba_debug_warp_ms(double* ms /*[4]*/, int64_t* n);
 
+/* --- before the detection table: sub-pixel refinement of detected corners ----------------------------------------------- */
+/* board.subpix_corners (board/common.py:50-54: cv2.cornerSubPix) for n corners in N grey images [N,H,W] of one size in one launch
+ * (csrc/mcba_subpix.h).  Pixel centres are at integer coordinates.  One iteration at the position c: bilinear
+ * samples S(i, j) of the image at c + (j, i) with one fractional offset and a replicate border; gx = S(i, j+1) - S(i, j-1),
+ * gy = S(i+1, j) - S(i-1, j) on the window |i| <= win_y, |j| <= win_x; weight m = e^-(i/win_y)^2 e^-(j/win_x)^2, zero where
+ * |i| <= zero_y and |j| <= zero_x if zero_x, zero_y >= 0 and the zone is smaller than the window on both axes (otherwise no zone);
+ * a = sum m gx^2, b = sum m gx gy, d = sum m gy^2, p = sum m (gx^2 j + gx gy i), q = sum m (gx gy j + gy^2 i); |a d - b^2| <=
+ * DBL_EPSILON^2 stops and keeps c; else c <- c + (d p - b q, a q - b p) / (a d - b^2).  The iteration stops when c leaves
+ * [0, W) x [0, H), when the squared step is <= eps^2, or after max_iter iterations; a result further from the start than win_x in x
+ * or win_y in y is given up for the start.  FP64 throughout (cv2 holds the patch and the result in float32: parity is at formula
+ * level).  refined [n,2] is the position the stopping rule leaves; status [n] MCBA_SUBPIX_*; iterations [n] (or NULL) the evaluations
+ * of the sums; quality [n] (or NULL) the smaller eigenvalue of [[a, b], [b, d]] / sum m at the last evaluation: the mean squared
+ * gradient along the weakest direction in grey levels squared, NaN when nothing was evaluated.  dtype MCBA_PIXEL_*.
+ * Handle-less, the error convention of the undistortion entries.  Refused with a message: a half window outside 1 .. 15, max_iter
+ * outside 1 .. 100, eps negative or not finite, an unknown pixel type, H or W below 2, an image index outside 0 .. N - 1 (the
+ * message names the first such corner).  n == 0 launches nothing.                                                            */
+#define MCBA_SUBPIX_OK 0           /* stopped on eps                                                                      */
+#define MCBA_SUBPIX_MAX_ITER 1     /* max_iter iterations without reaching eps                                            */
+#define MCBA_SUBPIX_SINGULAR 2     /* no gradient structure in the window: the position before that iteration             */
+#define MCBA_SUBPIX_LEFT_IMAGE 3   /* the iteration left the image                                                        */
+#define MCBA_SUBPIX_REVERTED 4     /* moved further than the window: the start is returned (overrides the others)         */
+#define MCBA_SUBPIX_INVALID 5      /* start not finite or outside the image: returned unchanged, nothing read             */
+int32_t mcba_refine_corners(const void* images, int32_t N, int32_t H, int32_t W, int32_t dtype, int32_t n,
+                            const double* corners /*[n][2]*/, const int32_t* image_of_corner /*[n] or NULL: image 0*/,
+                            int32_t win_x, int32_t win_y, int32_t zero_x, int32_t zero_y, int32_t max_iter, double eps,
+                            double* refined /*[n][2]*/, uint8_t* status /*[n]*/, int32_t* iterations /*[n] or NULL*/,
+                            double* quality /*[n] or NULL*/);
+/* timing of the last mcba_refine_corners call of this thread, milliseconds: [0] uploads, [1] k_refine_corners (HIP events), [2]
+ * downloads, [3] the whole call; *n (or NULL) = corners                                                                   */
+int32_t mcba_debug_subpix_ms(double* ms /*[4]*/, int64_t* n);
+
 /* --- solve -------------------------------------------------------------------------------------------------- */
 /* Trust-region least squares: replaces scipy.optimize.least_squares(method='trf', x_scale='jac', jac_sparsity=S,
  * loss, f_scale, ftol, max_nfev) at calibration.py:209-210.  x is updated in place to `res.x`.                 */

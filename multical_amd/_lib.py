@@ -176,6 +176,7 @@ RECON_OK, RECON_TOO_FEW, RECON_DEGENERATE, RECON_UNCONSTRAINED = 0, 1, 2, 3   # 
 RECON_MAX_CAMERAS = 8                                 # MCBA_RECON_MAX_CAMERAS
 PIXEL_U8, PIXEL_F32 = 0, 1                            # MCBA_PIXEL_*
 UNDISTORT_OK, UNDISTORT_NOT_CONVERGED = 0, 1          # MCBA_UNDISTORT_*
+SUBPIX_OK, SUBPIX_MAX_ITER, SUBPIX_SINGULAR, SUBPIX_LEFT_IMAGE, SUBPIX_REVERTED, SUBPIX_INVALID = 0, 1, 2, 3, 4, 5   # MCBA_SUBPIX_*
 
 LOG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p)
@@ -282,6 +283,10 @@ SYMBOLS = [
                                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_int32,
                                                   C.c_double, C.c_void_p]),
   ("mcba_debug_warp_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_refine_corners", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_int32_p,
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, c_double_p, c_uint8_p,
+                                      c_int32_p, c_double_p]),
+  ("mcba_debug_subpix_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_solve", C.c_int32, [H, c_double_p, C.POINTER(Options), C.POINTER(Result)]),
   ("mcba_time_linearize", C.c_int32, [H, c_double_p, C.POINTER(Options), C.c_int32, c_double_p]),
   ("mcba_time_residuals", C.c_int32, [H, c_double_p, C.c_int32, c_double_p]),

@@ -312,6 +312,33 @@ def make_point_table(detections, boards):
   return Table.create(points=points.reshape(C_, F, B, num_points, 2), valid=valid.reshape(C_, F, B, num_points))
 
 
+def refine_point_table(images, point_table, drop=(), **kw):
+  """Refine every valid corner of a point table (points [C, F, B, P, 2], valid [C, F, B, P]) to sub-pixel in the images it was found
+  in: images[c] is the [F, H, W] grey stack of camera c.  One subpix.refine_corners call per distinct image size (the cameras of one
+  size go together); kw: its window, zero_zone, max_iter, eps.  Returns (table, status [C, F, B, P] uint8) with the dtype of the
+  table kept, invalid slots untouched and their status subpix.INVALID.  drop: names of statuses ("singular", "reverted",
+  "left_image", ...) whose slots lose `valid`; by default nothing is dropped."""
+  from . import subpix
+  points, valid = np.array(point_table.points), np.array(point_table.valid, dtype=bool)
+  C_, F = valid.shape[:2]
+  stacks = [np.asarray(s) for s in images]
+  assert len(stacks) == C_ and all(s.ndim == 3 and s.shape[0] == F for s in stacks), "images[c] is the [F, H, W] stack of camera c"
+  status = np.full(valid.shape, subpix.INVALID, dtype=np.uint8)
+  for size in sorted({s.shape[1:] + (s.dtype.str,) for s in stacks}):
+    cams = [c for c in range(C_) if stacks[c].shape[1:] + (stacks[c].dtype.str,) == size]
+    c, f, b, p = np.nonzero(valid[cams])
+    if c.size == 0:
+      continue
+    c = np.array(cams)[c]
+    batch = np.concatenate([stacks[k] for k in cams])
+    image_of = (np.searchsorted(cams, c) * F + f).astype(np.int32)
+    refined, st = subpix.refine_corners(batch, points[c, f, b, p].astype(np.float64), image_of, **kw)[:2]
+    points[c, f, b, p] = refined.astype(points.dtype)
+    status[c, f, b, p] = st
+  dropped = np.isin(status, [subpix.STATUS_NAMES[name] for name in drop]) & valid
+  return point_table._extend(points=points, valid=valid & ~dropped), status
+
+
 # ---- the pose table: one board pose per view from its detections (tables.py:38-66, board/common.py:30-47) -----------------
 VIEW_OK, VIEW_TOO_FEW, VIEW_MASKED, VIEW_DEGENERATE, VIEW_NOT_CONVERGED = 0, 1, 2, 3, 4   # mcba.h: MCBA_VIEW_*
 
