@@ -592,6 +592,49 @@ int32_t mcba_rig_poses(const mcba_rig_pose_problem* p, double* poses, double* po
  * [2] refinement kernel (both by HIP events), [3] downloads, [4] the whole call; *n_frames (or NULL) = frames launched       */
 int32_t mcba_debug_rig_poses_ms(double* ms /*[5]*/, int64_t* n_frames);
 
+/* --- stereo calibration of camera pairs with the cameras held (batched stereoCalibrate) -------------------------------- */
+/* The relative pose of n_pairs pairs (l, r) of cameras of one detection table, every pair from its own common views, all pairs in
+ * one launch (csrc/mcba_stereo.h: one workgroup per pair, Levenberg-Marquardt over T_rel -- left-camera frame -> right-camera
+ * frame, X_r = R X_l + T, the reference's matrix.join(R, T) -- and one board pose per view, on the pixel residuals of the
+ * project's own projection in both cameras).  A view of a pair is a (frame, board) slot whose view_valid is set for both cameras
+ * and which holds at least min_common corners that are valid in both cameras and in board_valid, with finite pixels; only those
+ * corners enter; a slot whose common corners lie on one line (to 1e-6 of their extent) is dropped.  The view starts from the left
+ * camera's view_poses entry, T_rel from the best of up to four candidates T_{r,v} T_{l,v}^-1 of the views with the most common
+ * corners, scored over all the pair's views.  The model is cv2's static one with CALIB_FIX_INTRINSIC: no rolling shutter, no free
+ * intrinsics.  Handle-less like mcba_view_poses; same error convention, the caller owns every array.                        */
+#define MCBA_STEREO_OK 0              /* converged                                                                        */
+#define MCBA_STEREO_TOO_FEW 1         /* the pair has no view: no pose                                                    */
+#define MCBA_STEREO_DEGENERATE 2      /* all the pair has are slots of collinear common corners; or a vanishing pivot of a  */
+                                      /* scaled view block or of the scaled reduced matrix at the returned point, a cost     */
+                                      /* that is not finite, no start candidate with a finite score: no pose               */
+#define MCBA_STEREO_NOT_CONVERGED 3   /* max_iterations passes did not meet the step rule: the last iterate                */
+typedef struct mcba_stereo_problem {
+  mcba_camera_set cams;          /* C cameras */
+  int32_t F, B, P;               /* frames, boards, padded corners per board */
+  const double* board_points;    /* [B,P,3] board geometry, padded at the end of a row */
+  const uint8_t* board_valid;    /* [B,P] or NULL = every point */
+  const double* points;          /* [C,F,B,P,2] pixels */
+  const uint8_t* valid;          /* [C,F,B,P] */
+  const double* view_poses;      /* [C,F,B,4,4] start poses board -> camera (what mcba_view_poses returns) */
+  const uint8_t* view_valid;     /* [C,F,B] the start pose of the view may be used */
+  int32_t n_pairs;
+  const int32_t* pairs;          /* [n_pairs,2] left, right; l == r or an index out of range is an error */
+  int32_t min_common;            /* <= 0: 4; below 3 is an error */
+  int32_t max_iterations;        /* passes of the loop (rejected steps count); <= 0: 100, at most 1000 */
+  double sigma_px;               /* <= 0: the pair's own sse / (4 n_points - 6 - 6 n_views) */
+} mcba_stereo_problem;
+/* Outputs: T [n_pairs,4,4]; cov [n_pairs,6,6] = sigma^2 (H_rr - sum_v S_v)^-1 over (rx ry rz tx ty tz) of T_rel, the view poses
+ * eliminated, at the returned point; sse [n_pairs] squared pixel residuals of both cameras; n_views, n_points [n_pairs] views and
+ * common corners that entered (a corner counts once); iterations [n_pairs]; view_poses_out [n_pairs,F,B,4,4] board -> left
+ * camera, identity where the slot is no view of the pair; view_sse [n_pairs,F,B,2] left | right; status [n_pairs] MCBA_STEREO_*.
+ * Pairs without a result: identity, NaN covariance (also where the degree of freedom is not positive), sse 0.  Every output but
+ * T and status may be NULL.  Pairs without a view are not launched; n_pairs == 0 or no pair with a view touches no device.     */
+int32_t mcba_stereo_calibrate(const mcba_stereo_problem* p, double* T, double* cov, double* sse, int32_t* n_views, int32_t* n_points,
+                              int32_t* iterations, double* view_poses_out, double* view_sse, uint8_t* status);
+/* timing of the last mcba_stereo_calibrate call of this thread, milliseconds: [0] host preparation, [1] uploads, [3] downloads +
+ * scatter by host clock, [2] the kernel by HIP events around its launch; *n_pairs (or NULL) = pairs launched               */
+int32_t mcba_debug_stereo_calibrate_ms(double* ms /*[4]*/, int64_t* n_pairs);
+
 /* --- using a calibration: projection uncertainty where no board was ------------------------------------------------- */
 /* The 2 x 2 covariance of where a point projects into camera b when the shared parameters vary with their covariance
  * (csrc/mcba_uncertainty.h), for pixels anywhere in the image.  A job is one camera, one reference, one inverse

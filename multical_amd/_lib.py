@@ -101,6 +101,13 @@ class RigPoseProblem(C.Structure):   # mcba_rig_pose_problem
               ("image_heights", c_double_p), ("sigma_px", C.c_double), ("max_iterations", C.c_int32)]
 
 
+class StereoProblem(C.Structure):   # mcba_stereo_problem
+  _fields_ = [("cams", CameraSet), ("F", C.c_int32), ("B", C.c_int32), ("P", C.c_int32), ("board_points", c_double_p),
+              ("board_valid", c_uint8_p), ("points", c_double_p), ("valid", c_uint8_p), ("view_poses", c_double_p),
+              ("view_valid", c_uint8_p), ("n_pairs", C.c_int32), ("pairs", c_int32_p), ("min_common", C.c_int32),
+              ("max_iterations", C.c_int32), ("sigma_px", C.c_double)]
+
+
 class UncertaintyJob(C.Structure):   # mcba_uncertainty_job
   _fields_ = [("camera", C.c_int32), ("reference", C.c_int32), ("inv_distance", C.c_double), ("K", C.c_int32), ("r", C.c_int32),
               ("W", c_double_p), ("unconstrained", c_uint8_p), ("grid_w", C.c_int32), ("grid_h", C.c_int32), ("u0", C.c_double),
@@ -136,6 +143,7 @@ TRI_OK, TRI_TOO_FEW, TRI_DEGENERATE, TRI_NOT_CONVERGED, TRI_BEHIND = 0, 1, 2, 3,
 TRI_MAX_CAMERAS = 64                                  # MCBA_TRI_MAX_CAMERAS
 RIG_OK, RIG_TOO_FEW, RIG_DEGENERATE, RIG_NOT_CONVERGED, RIG_BEHIND = 0, 1, 2, 3, 4   # MCBA_RIG_*
 RIG_MAX_CAMERAS = 64                                  # MCBA_RIG_MAX_CAMERAS
+STEREO_OK, STEREO_TOO_FEW, STEREO_DEGENERATE, STEREO_NOT_CONVERGED = 0, 1, 2, 3   # MCBA_STEREO_*
 UNC_OK, UNC_NOT_CONVERGED, UNC_BEHIND, UNC_UNCONSTRAINED = 0, 1, 2, 3   # MCBA_UNC_*
 UNC_MAX_K = 48                                        # MCBA_UNC_MAX_K
 PDIFF_OK, PDIFF_NOT_CONVERGED, PDIFF_BEHIND, PDIFF_NO_FIT = 0, 1, 2, 3   # MCBA_PDIFF_*
@@ -230,6 +238,9 @@ SYMBOLS = [
   ("mcba_rig_poses", C.c_int32, [C.POINTER(RigPoseProblem), c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p,
                                  c_double_p, c_uint8_p]),
   ("mcba_debug_rig_poses_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
+  ("mcba_stereo_calibrate", C.c_int32, [C.POINTER(StereoProblem), c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_int32_p,
+                                        c_double_p, c_double_p, c_uint8_p]),
+  ("mcba_debug_stereo_calibrate_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),
   ("mcba_projection_uncertainty", C.c_int32, [C.POINTER(CameraSet), c_double_p, C.c_int32, C.POINTER(UncertaintyJob), c_double_p,
                                               c_double_p, c_uint8_p]),
   ("mcba_debug_projection_uncertainty_ms", C.c_int32, [c_double_p, C.POINTER(C.c_int64)]),

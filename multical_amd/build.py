@@ -24,7 +24,7 @@ SOURCES = ["mcba_api.hip", "mcba_cam_pin4.hip", "mcba_cam_pin5.hip", "mcba_cam_p
            "mcba_cam_pin14.hip", "mcba_cam_fish4.hip", "mcba_cam_mix14.hip", "mcba_pnp.hip", "mcba_intrinsic.hip",
            "mcba_handeye.hip", "mcba_undistort.hip", "mcba_triangulate.hip", "mcba_localize.hip",
            "mcba_uncertainty.hip", "mcba_projdiff.hip", "mcba_guidance.hip", "mcba_rigview.hip", "mcba_init.hip",
-           "mcba_recon.hip", "mcba_subpix.hip", "mcba_warp.hip"]
+           "mcba_recon.hip", "mcba_subpix.hip", "mcba_stereo.hip", "mcba_warp.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "mcba.h")]
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wall", "-Wno-unused-function"] + \
         (["-DMCBA_ENV_SWITCHES=1"] if VARIANT else []) + os.environ.get("MCBA_EXTRA_FLAGS", "").split()

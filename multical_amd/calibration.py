@@ -880,6 +880,79 @@ class Calibration(parameters.Parameters):
          f"quantiles={stats.quantiles}, median translation std={med:.6f}")
     return r
 
+  # --- every camera pair on its own, beside the rig ------------------------------------------------
+  PAIR_WARN_SCALE = 5.0      # reporting convention of report_pairwise_extrinsics: scaled difference above which a pair is pointed at
+
+  def pairwise_extrinsics(self, min_views=3, inliers_only=True, min_common=4, sigma=None):
+    """The relative pose of every camera pair from that pair's own common views (multical_amd.stereo: cameras held, one workgroup
+    per pair, all pairs in one launch), set beside the rig's camera_poses[j] @ inv(camera_poses[i]).  It says WHICH pair disagrees
+    with the joint bundle adjustment: a camera that was bumped, a wrong spanning-tree edge of the initialisation, a pair whose
+    overlap is too thin to trust.  The views start from the calibration's own chain camera . rig . board (the start pose under rolling
+    shutter), over its inliers (inliers_only) or valid points.
+
+    Returns the struct of stereo.calibrate_pairs (pairs i < j of valid cameras with a common view) extended by
+      T_rig [n, 4, 4]        the rig's relative pose of the pair
+      rotation_mrad [n]      rotation angle between the pair's estimate and the rig's, milliradians
+      translation_mm [n]     norm of the translation difference, in 1/1000 of the boards' unit (mm for boards in metres)
+      rotation_scaled, translation_scaled [n]   the differences in units of the pair's own standard deviation:
+                             sqrt(d^T C^-1 d) with C the rotation / translation block of the pair's covariance and d taken in the
+                             covariance's own parameters (stereo.scaled_difference: difference of the global rotation vectors)
+      scaled [n]             the larger of the two
+      enough [n]             the pair has a result and at least min_views views
+      ranking                indices of the pairs with `enough`, largest scaled difference first
+    The scaled difference is a SCALE, not a test: the two estimates share their data (the rig's comes from the same detections and
+    more), so it does not follow a chi distribution.  The pair model is static: under a rolling shutter it ignores the readout."""
+    from . import stereo
+    cam_ok, board_ok = np.asarray(self.camera_poses.valid).astype(bool), np.asarray(self.board_poses.valid).astype(bool)
+    start, _ = self._rig_poses()
+    chain = (np.asarray(self.camera_poses.poses)[:, None, None] @ np.asarray(start)[None, :, None] @
+             np.asarray(self.board_poses.poses)[None, None, :])
+    view_valid = cam_ok[:, None, None] & np.asarray(self.motion.valid).astype(bool)[None, :, None] & board_ok[None, None, :]
+    mask = np.asarray(self.inliers if inliers_only else self.valid).astype(bool)
+    board_points = [np.asarray(b.adjusted_points, dtype=np.float64) for b in self.boards]
+    pairs = stereo.common_view_pairs(mask, view_valid, min_common, stereo.pad_boards(board_points, mask.shape[3])[0])
+    r = stereo.calibrate_pairs(self.cameras, board_points, self.point_table.points, mask, chain, view_valid, pairs,
+                               min_common=min_common, sigma=sigma)
+    poses = np.asarray(self.camera_poses.poses)
+    T_rig = poses[pairs[:, 1]] @ np.linalg.inv(poses[pairs[:, 0]]) if len(pairs) else np.zeros((0, 4, 4))
+    have = (r.status == stereo.OK) | (r.status == stereo.NOT_CONVERGED)
+    # (the covariance is over the global rotation vector and the translation of T: the differences are taken in those parameters)
+    diff = stereo.scaled_difference(r.T, T_rig, r.cov)
+    angle = np.zeros(0)
+    if len(pairs):
+      angle = np.linalg.norm(stereo.rotation_vectors(r.T[:, :3, :3] @ np.swapaxes(T_rig[:, :3, :3], -1, -2)).reshape(-1, 3), axis=1)
+    d_t = diff.d_t
+    rot_s, t_s = np.where(have, diff.rotation, np.nan), np.where(have, diff.translation, np.nan)
+    both = np.fmax(rot_s, t_s)
+    enough = have & (r.n_views >= min_views) & np.isfinite(both)
+    idx = np.flatnonzero(enough)
+    ranking = idx[np.argsort(-both[idx], kind="stable")]
+    return r._extend(T_rig=T_rig, rotation_mrad=np.where(have, 1e3 * angle, np.nan),
+                     translation_mm=np.where(have, 1e3 * np.linalg.norm(d_t, axis=1), np.nan), rotation_scaled=rot_s,
+                     translation_scaled=t_s, scaled=both, enough=enough, ranking=ranking)
+
+  def report_pairwise_extrinsics(self, stage="", min_views=3):
+    """One line per camera pair through the "calibration" logger: views and points, the pair's RMS, the rotation (mrad) and
+    translation (mm) between the pair's own estimate and the rig's, and both in units of the pair's own standard deviation; pairs with
+    fewer than min_views views are listed as thin.  A warning goes to the pair with the largest scaled difference when it exceeds
+    Calibration.PAIR_WARN_SCALE (5): a reporting convention, not a test -- see pairwise_extrinsics.  Returns its struct."""
+    r = self.pairwise_extrinsics(min_views=min_views)
+    names = list(getattr(self.cameras, "names", [str(c) for c in range(len(self.cameras))]))
+    if hasattr(self.motion, "pose_start"):
+      info(f"{stage} pairwise extrinsics: the pair model is static and ignores the rolling-shutter readout; differences of the size of "
+           "the motion during a frame are expected")
+    for k, (i, j) in enumerate(r.pairs):
+      thin = "" if r.enough[k] else " (thin: not ranked)"
+      info(f"{stage} pair {names[i]}-{names[j]}: views={int(r.n_views[k])}, points={int(r.n_points[k])}, rms={r.rms[k]:.3f}, "
+           f"rotation={r.rotation_mrad[k]:.3f} mrad ({r.rotation_scaled[k]:.1f} sd), translation={r.translation_mm[k]:.3f} mm "
+           f"({r.translation_scaled[k]:.1f} sd){thin}")
+    if len(r.ranking) and r.scaled[r.ranking[0]] > self.PAIR_WARN_SCALE:
+      i, j = r.pairs[r.ranking[0]]
+      logger.warning(
+          f"{stage} pair {names[i]}-{names[j]} disagrees with the rig by {r.scaled[r.ranking[0]]:.1f} of its own standard deviations "
+          f"(reporting convention: above {self.PAIR_WARN_SCALE:g})")
+    return r
+
   # --- projection uncertainty where no board was (DESIGN.md 3.14) ----------------------------------------------------
   def _shared_layout(self):
     """(camera_index, pose_index): per camera, where its stored block (fx fy cx cy skew dist..) and its pose (rvec | tvec) sit in

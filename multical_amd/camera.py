@@ -302,3 +302,55 @@ def calibrate_cameras_fisheye(boards, points, image_sizes, max_iter=10, eps=1e-3
     _require_result(res, c)
     cameras.append(_camera_of(res, c, CameraFisheye, image_sizes[c], model, fix_aspect, has_skew, _solved_views(res, c, v)))
   return cameras, [float(e) for e in res.error]
+
+
+# ---- stereo calibration of a pair with the cameras held (camera.py:261-286, camera_fisheye.py:180-200) -------------------------
+def _start_poses(points, valid, board_points, cameras):
+  """The device call behind the start poses of the matched views (tables.view_poses); the host tests replace it."""
+  from . import tables
+  return tables.view_poses(points, valid, board_points, cameras)
+
+
+def _stereo_calibrate(cameras, matches, fix_intrinsic, who):
+  from . import stereo
+  if not fix_intrinsic:
+    raise NotImplementedError(f"{who}(fix_intrinsic=False): the pair model holds the cameras (cv2.CALIB_FIX_INTRINSIC); intrinsics and "
+                              "extrinsics are refined together by Calibration.bundle_adjust")
+  left, right = cameras
+  views = list(zip(matches.object_points, matches.points1, matches.points2))
+  n = len(views)
+  if n == 0:
+    raise RuntimeError(f"{who}: no matched views")
+  P = max(max(len(np.asarray(x)) for x, _, _ in views), 1)
+  # every matched view is a board of its own in a table of one frame: [2, 1, n, P]
+  points, valid, boards = np.zeros((2, 1, n, P, 2)), np.zeros((2, 1, n, P), dtype=bool), []
+  for b, (X, p1, p2) in enumerate(views):
+    X = np.asarray(X, dtype=np.float64).reshape(-1, 3)
+    points[0, 0, b, :len(X)] = np.asarray(p1, dtype=np.float64).reshape(-1, 2)
+    points[1, 0, b, :len(X)] = np.asarray(p2, dtype=np.float64).reshape(-1, 2)
+    valid[:, 0, b, :len(X)] = True
+    boards.append(X)
+  poses, _, _, status, _ = _start_poses(points, valid, boards, [left, right])
+  res = stereo.calibrate_pairs([left, right], boards, points, valid, poses, status == 0, [(0, 1)])
+  if res.status[0] not in (stereo.OK, stereo.NOT_CONVERGED):
+    raise RuntimeError(f"{who} failed: {stereo.STATUS_NAMES.get(int(res.status[0]), res.status[0])}")
+  return left.copy(), right.copy(), res.T[0], float(res.rms[0])
+
+
+def stereo_calibrate(cameras, matches, max_iter=60, eps=1e-6, fix_aspect=False, fix_intrinsic=True):
+  """camera.py:261-286 (cv2.stereoCalibrate with CALIB_USE_INTRINSIC_GUESS | CALIB_FIX_INTRINSIC): (left, right, pose, err) with
+  pose = matrix.join(R, T), left-camera frame -> right-camera frame.  matches: tables.matching_points' struct of parallel lists
+  object_points, points1, points2 -- one entry per view.
+
+  One device call (stereo.calibrate_pairs); the views start from their PnP pose in the left camera.  err = sqrt(sse / (2 n)) over the
+  pair's 2 n image points, believed to be cv2's return value (no cv2 binary was at hand to confirm it).  max_iter and eps are
+  accepted and UNUSED, as in Camera.calibrate here: the solve goes to the optimum of the reprojection cost, not to cv2's stop;
+  fix_aspect has nothing to act on while the intrinsics are held.  fix_intrinsic=False raises: Calibration.bundle_adjust refines
+  intrinsics and extrinsics together.  The two cameras need not share a model or an image size."""
+  return _stereo_calibrate(cameras, matches, fix_intrinsic, "stereo_calibrate")
+
+
+def stereo_calibrate_fisheye(cameras, matches, max_iter=60, eps=1e-6, fix_aspect=False, fix_intrinsic=True):
+  """camera_fisheye.py:180-200 (cv2.fisheye.stereoCalibrate): the same call as stereo_calibrate -- the projection of every camera
+  is switched at run time by its own family, so the two functions differ in name only."""
+  return _stereo_calibrate(cameras, matches, fix_intrinsic, "stereo_calibrate_fisheye")

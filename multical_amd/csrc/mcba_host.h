@@ -315,6 +315,7 @@ struct CallTiming {
 //     mark(i)          i == 0: the uploads are complete (synchronises) -> slot 0; records event i
 //     end_kernels()    launch status, synchronises; event i - 1 .. event i -> slot i; the downloads start here
 //     finish(count)    synchronises; downloads -> slot n, the whole call since construction -> slot n + 1, the count; then finish()
+//     finish_prepared(count)   instead of it, n = 2: host preparation | uploads | kernel | downloads (stereo pairs)
 struct DeviceCall {
   static constexpr int MAX_EVENTS = CallTiming::MAX_SLOTS - 2;
   CallTiming& tm;
@@ -362,6 +363,19 @@ struct DeviceCall {
     const double now = now_seconds();
     tm.ms[n_events] = (now - t_down) * 1e3;
     tm.ms[n_events + 1] = (now - t[0]) * 1e3;
+    tm.count = count;
+    finish();
+  }
+  // the four-slot layout of a call with ONE event-timed kernel whose host preparation is worth a slot of its own (the views of every
+  // stereo pair are counted on the host): after open(2), mark(0), mark(1), end_kernels() and the downloads,
+  //   host preparation (construction .. open) | uploads | kernel (events) | downloads, and the count; then finish()
+  void finish_prepared(int64_t count) {
+    HIP_OK(hipStreamSynchronize(st));
+    const double uploads = tm.ms[0], kernel = tm.ms[1];
+    tm.ms[0] = (t_up - t[0]) * 1e3;
+    tm.ms[1] = uploads;
+    tm.ms[2] = kernel;
+    tm.ms[3] = (now_seconds() - t_down) * 1e3;
     tm.count = count;
     finish();
   }

@@ -600,3 +600,36 @@ def calibrate_intrinsics(point_table, boards, image_sizes, model='standard', fix
   rc, out = inp.call(_lib.load().mcba_calibrate_intrinsics)
   check(rc)
   return out
+
+
+# ---- stereo pairs (tables.py:111-128, 380-382) ---------------------------------------------------------------------------------
+def matching_points(points, board, cam1, cam2):
+  """tables.matching_points (tables.py:115-128): the corners cameras cam1 and cam2 both detected, view by view, as a struct of
+  parallel lists points1, points2, object_points, ids.  points: a point table [C, F, P] of one board (the reference's form: one
+  entry per frame, empty ones included) or [C, F, B, P] with `board` a list of boards (one entry per (frame, board) slot, frame-major).
+  Boards are objects with `points`, or [P_b, 3] arrays."""
+  pts, valid = np.asarray(points.points, dtype=np.float64), np.asarray(points.valid).astype(bool)
+  if valid.ndim == 3:
+    pts, valid, board = pts[:, :, None], valid[:, :, None], [board]
+  elif not isinstance(board, (list, tuple)):
+    board = [board]
+  assert valid.ndim == 4 and len(board) == valid.shape[2], "one board per slot of the table's board axis"
+  board_points = [np.asarray(getattr(b, "points", b), dtype=np.float64) for b in board]
+  out = struct(points1=[], points2=[], object_points=[], ids=[])
+  for f in range(valid.shape[1]):
+    for b in range(valid.shape[2]):
+      ids = np.flatnonzero(valid[cam1, f, b] & valid[cam2, f, b])
+      out.points1.append(pts[cam1, f, b, ids])
+      out.points2.append(pts[cam2, f, b, ids])
+      out.object_points.append(board_points[b][ids])
+      out.ids.append(ids)
+  return out
+
+
+def stereo_calibrate(points, board, cameras, i, j, **kwargs):
+  """tables.stereo_calibrate (tables.py:380-382): camera.stereo_calibrate of cameras i and j on their matching points; a pair of
+  fisheye cameras goes to camera.stereo_calibrate_fisheye."""
+  from . import camera
+  matching = matching_points(points, board, i, j)
+  fn = camera.stereo_calibrate_fisheye if _is_fisheye(cameras[i]) and _is_fisheye(cameras[j]) else camera.stereo_calibrate
+  return fn((cameras[i], cameras[j]), matching, **kwargs)
